@@ -2,7 +2,7 @@
 """bench.py -- BPR-train interactions/sec of the LightGCN (d=64, L=3) + BPR + Adam step on the SYN-v1 synthetic
 1M-user x 100K-item graph (BASELINE.json configs[1]), on N MI355X GPUs of one node.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one iteration of the reference's training inner loop (recommender/LightGCN.py:47-64) at the reference's
@@ -53,7 +53,53 @@ def parse():
     ap.add_argument('--share-steps', type=int, default=30, help='steps of ONE rank\'s share of the N=8 step to time alone on this GPU (projected_ceiling_8gpu; 0 disables)')
     ap.add_argument('--l2-ceiling', type=int, default=1, help='measure the hop with every gather an L2 hit (roofline.attainable); 0 disables')
     ap.add_argument('--dense-step', action='store_true', help='time the reference-shaped step (all 2L hops on the full graph) as the main number')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one computed as DIR/<name>.npy (loss vector, seeded sample of the table rows; '
+                         'at most 64 MB): two builds run with the same arguments can be compared output for output')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
+
+
+DUMP_BYTES = 64 * 10**6        # --dump-outputs: bytes of all arrays together
+
+
+def dump_rows(U, I, d, seed):
+    """Rows of the [U+I, d] table that --dump-outputs writes: all of them if the table fits DUMP_BYTES, otherwise a sample drawn from `seed`
+    alone (every item row if the items fit in half the budget, user rows fill the rest), sorted.  The same arguments give the same rows."""
+    budget = (DUMP_BYTES - 4096) // (4 * d)                  # rows; 4 KB for the loss vector and the .npy headers
+    n_i = min(I, max(budget // 2, budget - U))
+    n_u = min(U, budget - n_i)
+    rng = np.random.default_rng(seed)
+    pick = lambda n_all, n: np.arange(n_all, dtype=np.int64) if n == n_all else np.sort(rng.choice(n_all, n, replace=False)).astype(np.int64)
+    return pick(U, n_u), pick(I, n_i)
+
+
+def capture_outputs(torch, eng, lo, U, I, d, seed, sharded):
+    """What a caller of the timed step holds after its last call: the loss vector it returned ([bpr, reg term, ||U_b||, ||P_b||]) and the updated
+    embedding table, as host arrays (table rows: dump_rows).  Under sharding every rank contributes its own user rows; the item rows are replicated."""
+    rows_u, rows_i = dump_rows(U, I, d, seed)
+    take = lambda rows: eng.E0.index_select(0, torch.from_numpy(rows).to(eng.E0.device)).cpu().numpy()
+    loss = lo.detach().cpu().numpy().astype(np.float32)
+    if not sharded:
+        return {'loss': loss, 'user_emb': take(rows_u), 'item_emb': take(U + rows_i)}
+    import torch.distributed as dist
+    mine = rows_u[(rows_u >= eng.u0) & (rows_u < eng.u1)]
+    parts = [None] * dist.get_world_size()
+    dist.all_gather_object(parts, (mine, take(mine - eng.u0)))
+    rows = np.concatenate([p[0] for p in parts])
+    user = np.concatenate([p[1] for p in parts])[np.argsort(rows, kind='stable')]
+    return {'loss': loss, 'user_emb': user, 'item_emb': take(eng.Ul + rows_i)}
+
+
+def write_outputs(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES and all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 class SpmmEvents:
@@ -709,6 +755,15 @@ def main():
     ev.on = False
     ops.EVENT_HOOK = None
     loss = float(lo[0] + lo[1])
+    dumped = None
+    if args.dump_outputs:
+        # the state after the last step of the region `ms_per_step` times (the regions below train on): copied outside every clock
+        outs = capture_outputs(torch, eng, lo, U, I, d, args.seed, sharded)
+        if rank == 0:
+            dumped = {'dir': args.dump_outputs, 'arrays': write_outputs(args.dump_outputs, outs), 'after_steps': n_batches,
+                      'rows': 'user_emb / item_emb: %d of %d user rows and %d of %d item rows of the table (sorted; seeded sample when the table exceeds %d bytes)'
+                              % (outs['user_emb'].shape[0], U, outs['item_emb'].shape[0], I, DUMP_BYTES)}
+        del outs
     comm_diag = comm_info = None
     if sharded:
         # diagnostic region (not part of any reported time): the same steps with an event pair around every wait on a collective -- per rank,
@@ -819,6 +874,8 @@ def main():
                                                      'note': '`attainable` above is THIS kernel with every gather an L2 hit; these are the guide\'s rates for the same bytes'}}
             else:
                 res['spmm_events_ms'] = {k: v[0] for k, v in evs.items()}
+        if dumped is not None:
+            res['dump_outputs'] = dumped
         if comm_info is not None:
             res['comm'] = comm_info
         if comm_diag is not None:

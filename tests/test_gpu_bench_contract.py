@@ -47,6 +47,43 @@ def test_bench_json_contract_small_instance():
     assert all(0.0 <= x <= 1.0 for x in sk['trained_propagated_tables'] + sk['random_tables'])
 
 
+def test_bench_dump_outputs_repeat_across_runs(tmp_path):
+    """--dump-outputs: the loss vector and the table rows after the last timed step, float32, within the budget.  Two runs with the same
+    arguments start from the same inputs, so they agree to the fp32 parity bar; a --gpus 2 run (user-sharded, rows gathered from both
+    ranks) agrees with them to twice that bar (each engine is held to RTOL against the oracle, tests/test_gpu_dist.py)."""
+    if not torch.cuda.is_available():
+        pytest.fail('GPU tests need a GPU')
+    import numpy as np
+    from conftest import close, rel_err, RTOL
+    import bench
+    U, I = 30000, 3000                                       # SYN-v1 keeps every user and covers every item
+    dumps = []
+    for run, gpus in (('a', 1), ('b', 1), ('c', 2)):
+        out = tmp_path / run
+        env = dict(os.environ)
+        env.pop('WORLD_SIZE', None); env.pop('RANK', None); env.pop('LOCAL_RANK', None)
+        if gpus > 1 and torch.cuda.device_count() < 2:
+            env['ARL_BENCH_SINGLE_DEVICE'] = '1'; env['ARL_BENCH_BACKEND'] = 'gloo'
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(gpus), '--users', str(U), '--items', str(I), '--steps', '4', '--warmup', '1',
+               '--repeats', '1', '--attack-steps', '0', '--cpu-baseline', '0', '--api-steps', '0', '--model-steps', '0', '--share-steps', '0',
+               '--l2-ceiling', '0', '--dump-outputs', str(out)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        r = json.loads(lines[0])
+        assert r['n_gpus'] == gpus and r['steps'] == 4 and r['dump_outputs']['after_steps'] == 5
+        arrays = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert sorted(arrays) == ['item_emb', 'loss', 'user_emb']
+        assert all(a.dtype == np.float32 for a in arrays.values()) and sum(os.path.getsize(out / f) for f in os.listdir(out)) <= bench.DUMP_BYTES
+        assert arrays['loss'].shape == (4,) and abs(float(arrays['loss'][0] + arrays['loss'][1]) - r['final_loss']) <= 1e-6 * abs(r['final_loss'])
+        assert arrays['user_emb'].shape == (U, 64) and arrays['item_emb'].shape == (I, 64)          # small tables go out whole
+        dumps.append(arrays)
+    for name in ('loss', 'user_emb', 'item_emb'):
+        assert close(dumps[0][name], dumps[1][name]), name
+        assert rel_err(dumps[2][name], dumps[0][name]) < 2 * RTOL, name
+
+
 def test_bench_gpus2_plain_invocation_self_launches():
     """`python bench.py --gpus 2` started the way the driver starts `--gpus 1` (no launcher, no WORLD_SIZE): bench.py starts its two ranks itself
     (child processes, before the parent touches the GPU) and prints the one JSON line with n_gpus 2 and the communication evidence.  On a 1-GPU
