@@ -10,20 +10,21 @@ import torch
 
 from ... import ops
 from ._bilevel import ScheduledBiLevel
+from .._common import cw_term
 from .CLeaR import _packed
 from .DLAttack import masked_topk
 
 
 class _CwLoss(torch.autograd.Function):
-    """CW loss and its gradient on the packed table straight from the top-k lists (ops.cw_topk_term: no U*T index lists, no operator build,
-    deterministic)."""
+    """CW loss and its gradient on the packed table straight from the top-k lists (ops.cw_topk_term, or _common.cw_term_rows past its limits: no
+    U*T index lists, no operator build, deterministic)."""
 
     @staticmethod
     def forward(ctx, Pu, Pi, top_idx, n_real, targets):
         X = _packed(Pu, Pi)
         Up = Pu.shape[0]
         tg = targets.to(X.device, torch.int64) if isinstance(targets, torch.Tensor) else torch.as_tensor(targets, device=X.device, dtype=torch.int64)
-        loss, G, _ = ops.cw_topk_term(X.contiguous(), Up, n_real, top_idx.contiguous(), tg, want_w=False, check_range=False)
+        loss, G, _ = cw_term(X.contiguous(), Up, n_real, top_idx.contiguous(), tg, want_w=False, check_range=False)
         ctx.save_for_backward(G)
         ctx.Up = Up
         return loss[0]

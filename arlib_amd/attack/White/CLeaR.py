@@ -16,7 +16,7 @@ import torch
 
 from ... import ops
 from ...util.metrics import AttackMetric
-from .._common import AttackBase, DEVICE, symmetric_adjacency, init_graph, rebuild_interaction_matrix, reinit_with_tables, cw_pairs, with_fake_rows, append_rows
+from .._common import AttackBase, DEVICE, symmetric_adjacency, init_graph, rebuild_interaction_matrix, reinit_with_tables, cw_pairs, cw_term, with_fake_rows, append_rows
 from ...util.optim import Adam        # torch.optim.Adam, stepped by arl_adam_dense_f32
 from .DLAttack import masked_topk, device_mask
 
@@ -44,7 +44,8 @@ class _CwSfaLoss(torch.autograd.Function):
         tg = targets.to(X.device, torch.int64) if isinstance(targets, torch.Tensor) else torch.as_tensor(targets, device=X.device, dtype=torch.int64)
         # one hand-written kernel group (arl_cw_topk_term_f32): the loss, its gradient on every row and the SFA term's row multiplicities straight from the
         # top-k lists -- no operator build (sort, searchsorted, scatters), no ATen launches between the scoring pass and the SFA kernels, deterministic
-        cw1, G_cw, w = ops.cw_topk_term(X.contiguous(), Up, n_real, top_idx.contiguous(), tg, check_range=False)
+        # (past the kernel's limits -- T > 64, more items than its groups cover -- the same term on row primitives, _common.cw_term_rows)
+        cw1, G_cw, w = cw_term(X.contiguous(), Up, n_real, top_idx.contiguous(), tg, check_range=False)
         cw = cw1[0]
         sfa, G_sfa = ops.sfa_l1(X, w, r0.to(X.device, torch.float32).contiguous(), 3 * n_real * T * d)
         ctx.save_for_backward(G_cw, G_sfa)

@@ -3,6 +3,7 @@ import numpy as np
 import scipy.sparse as sp
 import torch
 
+from .. import ops
 from ..util.tool import targetItemSelect
 
 DEVICE = 'cuda'
@@ -73,6 +74,56 @@ def cw_pairs(top_idx, n_real_users, targets, pop=True):
         ranks = torch.full((n_real_users * T,), k - 1, device=top_idx.device, dtype=torch.long)
     neg = top_idx[users, ranks].long()
     return users, pos, neg
+
+
+def cw_term(X, n_user_rows, n_real, top_idx, targets, c=None, want_w=True, check_range=True, kern=None):
+    """The attacks' CW term with ops.cw_topk_term's contract (loss[1], G, w): on the kernel group where it takes the shape
+    (ops.cw_topk_term_supported), otherwise cw_term_rows -- T > 64 targets (the reference allows any T <= topk, CLeaR.py:60-88) or more items
+    than the kernel's item groups cover (a fractional targetSize, util/tool.py:56-60, on a large catalogue).  kern: the kernel module (ops)."""
+    kern = ops if kern is None else kern
+    Up, T, k = int(n_user_rows), targets.numel(), top_idx.shape[1]
+    if not 0 < T <= k:
+        raise ValueError('cw_term: 1 <= T <= k targets needed (T = %d, k = %d): a list has only k entries to pop' % (T, k))
+    if ops.cw_topk_term_supported(X.shape[0] - Up, X.shape[1], T, k):
+        return kern.cw_topk_term(X, Up, n_real, top_idx, targets, c=c, want_w=want_w, check_range=check_range)
+    return cw_term_rows(X, Up, n_real, top_idx, targets, c=c, want_w=want_w, check_range=check_range, kern=kern)
+
+
+def cw_term_rows(X, n_user_rows, n_real, top_idx, targets, c=None, want_w=True, check_range=True, kern=None):
+    """ops.cw_topk_term restated on row primitives, for any T <= k and any item count: per target, one gather of the negatives' rows and one
+    ORDERED scatter-add of the real users' rows into them (kern.gather_rows / kern.scatter_add_rows), so the result is deterministic.  A
+    target listed m times counts m times (cw_finish_kernel's tc).  X: contiguous [n_user_rows + I, d]; targets: int64 item ids."""
+    kern = ops if kern is None else kern
+    N, d = X.shape
+    Up, n_real = int(n_user_rows), int(n_real)
+    I, k, T = N - Up, top_idx.shape[1], targets.numel()
+    if not (0 < Up < N) or not (0 <= n_real <= Up) or top_idx.shape[0] < n_real or not (0 < T <= k):
+        raise ValueError('cw_term_rows: X [n_user_rows + I, d], top_idx [>= n_real, k], 1 <= T <= k')
+    neg = top_idx[:n_real, k - T:].flip(1).long()                              # column t = rank k - 1 - t: successive .pop()s (CLeaR.py:84-88)
+    if check_range and n_real and (int(neg.min()) < 0 or int(neg.max()) >= I or int(targets.min()) < 0 or int(targets.max()) >= I):
+        raise IndexError('cw_term_rows: item id out of range')
+    c = 1.0 / (max(n_real, 1) * T) if c is None else float(c)
+    G = torch.zeros_like(X)
+    w = torch.zeros(N, dtype=torch.float32, device=X.device) if want_w else None
+    loss = torch.zeros(1, dtype=torch.float32, device=X.device)
+    if n_real == 0:                                                            # no pairs: loss, G and w are 0 (the kernel's formula with n_real = 0)
+        return loss, G, w
+    ue = X[:n_real]
+    sum_u = ue.sum(0)
+    xt = X[Up + targets.long()]                                                # [T, d]
+    tg, tc = torch.unique(targets.long(), return_counts=True)                 # repeated targets: tc pulls of the same row
+    for t in range(T):
+        rows = (neg[:, t] + Up).to(torch.int32).contiguous()
+        ne = kern.gather_rows(X, rows, check_range=False)
+        loss += c * ((ue * ne).sum() - (sum_u * xt[t]).sum())
+        G[:n_real] += c * (ne - xt[t])
+        kern.scatter_add_rows(G, rows, ue, c, check_range=False)
+    G[Up + tg] -= (c * tc.to(X.dtype))[:, None] * sum_u                         # every pair pulls its target: -c * sum of the real users' rows
+    if want_w:
+        w[:n_real] = float(T)
+        w[Up:] = torch.bincount(neg.reshape(-1), minlength=I).to(torch.float32)
+        w[Up + tg] += tc.to(torch.float32) * float(n_real)
+    return loss, G, w
 
 
 def with_fake_rows(ui, first_fake_row, block):

@@ -2515,7 +2515,8 @@ __global__ __launch_bounds__(64 * topk_waves(D, SPLIT), ARL_TOPK_MIN_WAVES_EU) v
     // tables, lowered by a bound on the difference between this plain fp32 dot product and the streamed contraction, give a valid
     // starting threshold: all k candidates will pass it when they stream by, so the result is unchanged, but the ~k ln(I/k)
     // record-setters of a cold stream shrink to about k.  (A candidate that has become masked breaks the guarantee: rows that end
-    // with fewer than k keys raise `underflow` and the caller repeats the call cold.)
+    // with fewer than k keys raise `underflow` and the caller repeats the call cold.)  A user with fewer than k unmasked items starts
+    // at -inf: the tail of its list is masked items (-10e8), which no threshold from the candidates' unmasked scores lets through.
     float thr0v = -INFINITY;                                       // lane r: starting threshold of user row r
     if constexpr (WARM) {
         for (int r = 0; r < 16; ++r) {
@@ -2534,7 +2535,7 @@ __global__ __launch_bounds__(64 * topk_waves(D, SPLIT), ARL_TOPK_MIN_WAVES_EU) v
             float lb = lane < k ? (sdot - 8e-6f * sqrtf(nu * ni)) * score_scale - 1e-30f : INFINITY;     // thresholds live in the scaled domain
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) lb = fminf(lb, __shfl_xor(lb, off));
-            if (lane == r) thr0v = lb;
+            if (lane == r) thr0v = (mrp != nullptr && I - (mrp[u + 1] - mrp[u]) < k) ? -INFINITY : lb;
         }
     }
     float thrf[4];                                                 // exact running k-th best score of user rows 4g + reg (pre-filter)
@@ -3253,7 +3254,8 @@ __global__ __launch_bounds__(64 * topk_waves(D, SPLIT), ARL_TOPK_MIN_WAVES_EU) v
             top_val[(size_t)u * k + lane] = cand_score(key) * score_unscale;
             // the warm threshold excluded too much: the list ends short -- or with an interacted item's -10e8, which only belongs there when fewer than k
             // other items exist (a warm candidate that has become interacted can set a threshold above every free item; the repeat is then cold)
-            if (WARM && lane == k - 1 && (key == 0ull || cand_score(key) <= -5e8f * score_scale)) atomicOr(underflow, 1);
+            if (WARM && lane == k - 1 && (key == 0ull || cand_score(key) <= -5e8f * score_scale) && (mrp == nullptr || I - (mrp[u + 1] - mrp[u]) >= k))
+                atomicOr(underflow, 1);
         }
     }
 #ifdef ARL_TOPK_PROF
@@ -3320,9 +3322,9 @@ __host__ __device__ constexpr size_t t2_lds_bytes(int D, bool masked) {
 }
 
 // starting thresholds from the warm-start candidates (first form: the WARM prologue): thr0[u] = the lowest of the k candidates' fp32 scores, lowered by
-// the bound on the difference to the streamed contraction, in the scaled domain
+// the bound on the difference to the streamed contraction, in the scaled domain; -inf for a user with fewer than k unmasked items (as the first form)
 __global__ __launch_bounds__(kBlock) void topk2_warm_kernel(const float *__restrict__ Pu, const float *__restrict__ Pi_f32, int U, int I, int D, int k,
-                                                            const int32_t *__restrict__ warm_idx, const unsigned *__restrict__ table_max_bits,
+                                                            const int32_t *__restrict__ mrp, const int32_t *__restrict__ warm_idx, const unsigned *__restrict__ table_max_bits,
                                                             float *__restrict__ thr0, const int *__restrict__ gate, const int *__restrict__ gate2) {
     if (gate != nullptr && *gate == 0) return;
     if (gate2 != nullptr && *gate2 == 0) return;
@@ -3345,7 +3347,7 @@ __global__ __launch_bounds__(kBlock) void topk2_warm_kernel(const float *__restr
             if (j < k) lb = fminf(lb, v);
         }
         for (int off = LPR; off < 64; off <<= 1) lb = fminf(lb, __shfl_xor(lb, off));
-        if (lane == 0) thr0[u] = lb;
+        if (lane == 0) thr0[u] = (mrp != nullptr && I - (mrp[u + 1] - mrp[u]) < k) ? -INFINITY : lb;
     }
 }
 
@@ -3819,7 +3821,8 @@ __global__ __launch_bounds__(64 * kT2Waves) void topk2_main_kernel(const _Float1
             const unsigned long long key = ((unsigned long long)kh << 32) | kl;
             top_idx[(size_t)ur * k + lane] = cand_item(key);
             top_val[(size_t)ur * k + lane] = cand_score(key) * score_unscale;
-            if (warm && lane == k - 1 && (key == 0ull || cand_score(key) <= -5e8f * score_scale)) atomicOr(underflow, 1);      // (as the first form)
+            if (warm && lane == k - 1 && (key == 0ull || cand_score(key) <= -5e8f * score_scale) && (mrp == nullptr || I - (mrp[ur + 1] - mrp[ur]) >= k))
+                atomicOr(underflow, 1);                                                                                   // (as the first form)
         }
     }
 #ifdef ARL_TOPK2_PROF
@@ -5181,7 +5184,7 @@ int arl_score_mask_topk_f32(const float *Pu, const float *Pi, int64_t U, int64_t
 #define ARL_TOPK2_PASS(DV, WARMF, GATE)                                                                                                \
             do {                                                                                                                       \
                 if (WARMF) {                                                                                                           \
-                    hipLaunchKernelGGL(topk2_warm_kernel, dim3(grid_for(U, kWavesPerBlock, 8192u)), dim3(kBlock), 0, st, Pu, Pi, (int)U, (int)I, (int)d, (int)k, warm_idx, max_bits, thr0, GATE, \
+                    hipLaunchKernelGGL(topk2_warm_kernel, dim3(grid_for(U, kWavesPerBlock, 8192u)), dim3(kBlock), 0, st, Pu, Pi, (int)U, (int)I, (int)d, (int)k, mask_rowptr, warm_idx, max_bits, thr0, GATE, \
                                        (const int *)nullptr);                                                                          \
                     ARL_LAUNCH_CHECK();                                                                                                \
                 }                                                                                                                      \

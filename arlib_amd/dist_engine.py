@@ -25,6 +25,8 @@ import contextlib
 import numpy as np
 import torch
 
+from .attack._common import cw_term
+
 
 class _TimedWork:
     """all_reduce handle whose wait() is bracketed by two events on the compute stream: their distance is the time the compute stream
@@ -333,32 +335,15 @@ class ShardedPropagationEngine:
         nl = int(min(max(int(n_real) - self.u0, 0), Ul))              # local real users: rows [0, nl)
         tg = torch.as_tensor(list(targets), dtype=torch.int64, device=dev)
         c = 1.0 / (float(n_real) * T)
-        fused_cw = hasattr(k, 'cw_topk_term') and nl > 0               # the hand-written CW term (the oracle-backed CPU test double has none)
-        if fused_cw:
+        if nl > 0:
             # local real users x targets against the replicated item rows: loss share, dL/d(out) (user rows complete, item rows this rank's partial)
-            # and the SFA multiplicities of the local rows, in one kernel group
-            lo, G, w = k.cw_topk_term(out.contiguous(), Ul, nl, top_idx.contiguous(), tg, c=c, check_range=False)
+            # and the SFA multiplicities of the local rows -- one kernel group, or its row-primitive restatement past the kernel's limits
+            lo, G, w = cw_term(out.contiguous(), Ul, nl, top_idx.contiguous(), tg, c=c, check_range=False, kern=k)
             cw_local = lo[0]
         else:
             G = torch.zeros_like(out)
             w = torch.zeros(self.Nl, dtype=torch.float32, device=dev)
             cw_local = torch.zeros((), dtype=torch.float32, device=dev)
-        if nl and not fused_cw:
-            ue = out[:nl]
-            ranks = top_idx.shape[1] - 1 - torch.arange(T, device=dev)                  # successive .pop()s (CLeaR.py:84-88)
-            neg = top_idx[:nl][:, ranks].long()                                         # [nl, T]
-            tgt_rows = out[Ul + tg]                                                     # [T, d]
-            sum_u = ue.sum(0)
-            for t in range(T):
-                nrows = (neg[:, t] + Ul).to(torch.int32).contiguous()
-                ne = k.gather_rows(out, nrows, check_range=False)
-                cw_local = cw_local + c * ((ue * ne).sum() - (sum_u * tgt_rows[t]).sum())
-                G[:nl] += c * (ne - tgt_rows[t])
-                k.scatter_add_rows(G, nrows, ue.contiguous(), c, check_range=False)
-            G[Ul + tg] -= c * sum_u                                                     # every pair pulls its target: -c * sum of the local real users' rows
-            w[:nl] = float(T)
-            w[Ul:] = torch.bincount(neg.reshape(-1), minlength=self.I).to(torch.float32)
-            w[Ul + tg] += float(nl)
         if r0 is None:
             raise ValueError('step_clear: r0 must be given (the same d-vector on every rank)')
         st = k.SfaStages(out.contiguous(), w, r0.to(dev, torch.float32).contiguous())

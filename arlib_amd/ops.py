@@ -1209,13 +1209,24 @@ def pga_update_(S, grad, dinv_rows=None, dinv_cols=None):
 
 
 _CW_WS = {}
+CW_MAX_TARGETS = 64            # arl_cw_topk_term_f32's limits (arl_kernels.hip): targets per list,
+CW_MAX_GROUPS = 8192           # item groups of 128 rows (64 at d > 128) -- the group histograms live in LDS
+
+
+def cw_topk_term_supported(I, d, T, k):
+    """Whether arl_cw_topk_term_f32 takes I items of width d with T targets on top-k lists (the C entry's shape checks; it returns
+    ARL_E_DIM / ARL_E_ARG / ARL_E_RANGE otherwise).  attack._common.cw_term routes the other shapes to cw_term_rows."""
+    I, d, T, k = int(I), int(d), int(T), int(k)
+    ipg = 128 if d <= 128 else 64
+    return 0 < d <= 256 and d % 4 == 0 and 0 < T <= min(k, CW_MAX_TARGETS) and I > 0 and (I + ipg - 1) // ipg <= CW_MAX_GROUPS
 
 
 def cw_topk_term(X, n_user_rows, n_real, top_idx, targets, c=None, want_w=True, check_range=True):
     """CW term of the attacks' surrogate loss from the users' top-k lists (attack/White/CLeaR.py:83-95, PGA.py:104-116) on the packed table
     X [n_user_rows + I, d]: pairs (real user u < n_real) x (target t), negative = top_idx[u][k - 1 - t].  Returns (loss[1], G [like X], w) with
     loss = c * sum <X_u, X_neg - X_tg> (c defaults to 1 / (n_real T): the reference's mean), G = d loss / d X, and w (want_w) the SFA term's row
-    multiplicities (CLeaR.py:98-103).  targets: int64 device tensor of item ids.  Deterministic (64-bit fixed-point item sums), five launches."""
+    multiplicities (CLeaR.py:98-103).  targets: int64 device tensor of item ids.  Deterministic (64-bit fixed-point item sums), five launches.
+    Shapes: cw_topk_term_supported(I, d, T, k) (ValueError / ArlError otherwise; attack._common.cw_term falls back past them)."""
     _dev(X, torch.float32, 'X', 2); _dev(top_idx, torch.int32, 'top_idx', 2); _dev(targets, torch.int64, 'targets', 1)
     N, d = X.shape
     Up, n_real = int(n_user_rows), int(n_real)
@@ -1298,7 +1309,10 @@ def score_mask_topk(Pu, Pi, k, mask_rowptr=None, mask_col=None, exact=False, war
     cold automatically.
     item_order: 'norm' (default) streams the items by descending row norm on the fp16 matrix path when the stream is long enough for a
     bootstrap pass -- thresholds rise earlier, same result bit for bit (ids, values and tie order are those of the table order); None =
-    table order; or an int32 permutation of [0, I)."""
+    table order; or an int32 permutation of [0, I).
+    mask_rowptr / mask_col: each row holds SORTED, DISTINCT item ids in [0, I) -- the kernels find a candidate in its row by binary search, and a
+    row's count of unmasked items is I minus its length (a warm-started user with fewer than k unmasked items starts without a threshold: the
+    tail of its list is masked items at -10e8).  Not checked here (an O(nnz) pass per call)."""
     _dev(Pu, torch.float32, 'Pu', 2); _dev(Pi, torch.float32, 'Pi', 2)
     U, d = Pu.shape
     I = Pi.shape[0]

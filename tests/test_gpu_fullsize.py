@@ -9,6 +9,7 @@ properties -- the oracle cannot run this size in seconds, so the checks are iden
 import numpy as np
 import pytest
 import torch
+from conftest import close
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -228,6 +229,83 @@ def test_sfa_full_size_against_float64_closed_form(cfg2):
     Gd = wd[:, None] * ((A / (numel * Q)) * torch.sign(s)[:, None] * r[None, :] + q[:, None] * g_r[None, :] + (Xd @ g_r)[:, None] * r0d[None, :])
     assert abs(loss.item() - (S * A / (numel * Q)).item()) <= 1e-4 * abs((S * A / (numel * Q)).item())
     assert ((G.double() - Gd).norm() / Gd.norm()).item() < 1e-4
+
+
+def test_cw_term_full_size_against_float64(cfg2):
+    """CLeaR's CW term at cfg2 (arl_cw_topk_term_f32): propagated tables plus 64 fake rows, the masked top-50 of all 1 M real users, T = 5
+    targets (item 0, item I - 1, the most popular item and two others) -- 5 M (user, negative) entries over 782 item groups, the popular items'
+    groups cut into several slices -- against float64 on the device (user rows gathered, item rows summed by index_add_ in double): loss within
+    1e-5, G by close(), w equal to the negatives' histogram.  Deterministic, and the fallback (attack._common.cw_term_rows) gives the same term."""
+    import time
+    from arlib_amd.attack._common import cw_term_rows
+    ops, U, I, nnz = cfg2['ops'], cfg2['U'], cfg2['I'], cfg2['nnz']
+    F, T, k = 64, 5, 50
+    torch.manual_seed(4)
+    E = torch.cat([torch.nn.init.xavier_uniform_(torch.empty(U, 64)), torch.nn.init.xavier_uniform_(torch.empty(I, 64))], 0).to(DEV)
+    X, H = E.clone(), E
+    for _ in range(3):                                                         # LightGCN's output (mean of the L = 3 layers): what CLeaR scores
+        H = ops.spmm(cfg2['A'], H)
+        X += H
+    X /= 4
+    # the popularity direction trained tables carry (every user ranks the popular items high, so the tails of 1 M lists meet on few items): one
+    # vector v on every user row, and on the item rows in proportion to sqrt(degree) -- from random tables alone the tails spread evenly over the
+    # groups (< 8 192 entries each)
+    sdeg = torch.from_numpy(np.sqrt(np.diff(cfg2['rowptr'][U:])).astype(np.float32)).to(DEV)
+    v = torch.nn.functional.normalize(torch.randn(64, device=DEV), dim=0)
+    m = X.abs().mean()
+    X[:U] += 32.0 * m * v
+    X[U:] += (32.0 * m / sdeg.max()) * sdeg[:, None] * v[None, :]
+    Pu, Pi = X[:U].contiguous(), X[U:].contiguous()
+    rp = torch.from_numpy(cfg2['rowptr'][:U + 1].astype(np.int32)).to(DEV)
+    mc = (cfg2['A'].col[:nnz] - U).to(torch.int32).contiguous()
+    top, _ = ops.score_mask_topk(Pu, Pi, k, rp, mc)
+    Up = U + F
+    Xp = torch.cat([Pu, torch.randn(F, 64, device=DEV) * Pu.abs().max() * 0.1, Pi], 0).contiguous()
+    popular = int(np.diff(cfg2['rowptr'][U:]).argmax())
+    tg = torch.tensor(list(dict.fromkeys([0, I - 1, popular, 4711, 77_777])), dtype=torch.int64, device=DEV)
+    assert tg.numel() == T
+    neg = top[:, k - T:].flip(1).long()                                        # column t = rank k - 1 - t
+    per_group = torch.bincount(neg.reshape(-1) // 128)
+    print('cw term at cfg2: largest item group %d entries, %d groups over one slice' % (int(per_group.max()), int((per_group > 8192).sum())))
+    assert int(per_group.max()) > 8192                                         # multi-slice groups at full size
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    loss, G, w = ops.cw_topk_term(Xp, Up, U, top, tg)
+    torch.cuda.synchronize(); t_kernel = time.perf_counter() - t0
+    l2, G2, w2 = ops.cw_topk_term(Xp, Up, U, top, tg)
+    assert torch.equal(loss, l2) and torch.equal(G, G2) and torch.equal(w, w2)
+    t0 = time.perf_counter()
+    Xd = Xp.double()
+    c = 1.0 / (U * T)
+    ue = Xd[:U]
+    sum_u, negsum = ue.sum(0), torch.zeros(U, 64, dtype=torch.float64, device=DEV)
+    Gd = torch.zeros_like(Xd)
+    for t in range(T):
+        negsum += Xd[Up + neg[:, t]]
+        Gd[Up:].index_add_(0, neg[:, t], c * ue)
+        Gd[Up + tg[t]] -= c * sum_u
+    tsum = Xd[Up + tg].sum(0)
+    Gd[:U] = c * (negsum - tsum)
+    ref_loss = c * ((ue * negsum).sum() - (sum_u * tsum).sum()).item()
+    wd = torch.zeros(Up + I, dtype=torch.float64, device=DEV)
+    wd[:U] = T
+    wd[Up:] = torch.bincount(neg.reshape(-1), minlength=I).double()
+    wd[Up + tg] += float(U)
+    torch.cuda.synchronize(); t_ref = time.perf_counter() - t0
+    assert abs(loss.item() - ref_loss) <= 1e-5 * abs(ref_loss), (loss.item(), ref_loss)
+    assert close(G.cpu().numpy(), Gd.cpu().numpy())
+    assert torch.equal(w, wd.float()) and not bool(G[U:Up].any())
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    lf, Gf, wf = cw_term_rows(Xp, Up, U, top, tg)
+    torch.cuda.synchronize(); t_rows = time.perf_counter() - t0
+    assert abs(lf.item() - ref_loss) <= 1e-5 * abs(ref_loss) and close(Gf.cpu().numpy(), Gd.cpu().numpy()) and torch.equal(wf, w)
+    top80 = torch.randint(0, I, (U, 80), device=DEV, dtype=torch.int32)       # T = 70 > 64: only the fallback takes it
+    tg70 = torch.arange(70, dtype=torch.int64, device=DEV) * 1000
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    l70, _, w70 = cw_term_rows(Xp, Up, U, top80, tg70)
+    torch.cuda.synchronize(); t_rows70 = time.perf_counter() - t0
+    assert bool(torch.isfinite(l70).all()) and float(w70.sum()) == 3 * 70.0 * U
+    print('cw term at cfg2 (1 M users): kernel %.2f ms (T = 5), row fallback %.2f ms (T = 5) / %.2f ms (T = 70), float64 reference %.2f s'
+          % (1e3 * t_kernel, 1e3 * t_rows, 1e3 * t_rows70, t_ref))
 
 
 def test_pga_gradient_step_full_size_against_oracle(cfg2):
