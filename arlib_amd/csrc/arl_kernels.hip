@@ -1664,6 +1664,318 @@ __global__ __launch_bounds__(kBlock) void ngcf_wgrad_fold_kernel(const float *__
     }
 }
 // ================================================================================================
+// NCF MLP tower (recommender/NCF.py:203-220): t = relu(W2 relu(W1 relu(W0 x + b0) + b1) + b2) on every row x of the MLP table, and the
+// scored row [mf row | t] of width 2 d, in one kernel on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation).
+// The product is evaluated TRANSPOSED, h^T = W x^T: the weights (nn.Linear layout [out, in], row-major) are the A operand, read as one float4
+// per lane straight from L2 (lane (c, q) of output tile m, k-group g: W[16 m + c][16 g + 4 q .. + 3]); the rows are the B operand.  With the
+// k order permuted inside a group of 16 (step j of group g feeds k = 16 g + 4 q + j to lane group q, as in the NGCF kernel above) the C layout
+// of one layer -- lane (c, q) holds h[row c][16 m + 4 q + i], i < 4 -- IS the B layout of the next: h1 [16, 5d] and h2 [16, 2d] of a wave's
+// row tiles stay in registers between the layers, bias and ReLU run on them in place, nothing but the output (and, for the rows form, the
+// activations backward needs) is written.  A wave owns NB row tiles of 16 (NB = 4 / 4 / 2 / 1 for d = 16 / 32 / 64 / 128: h1 of its rows is
+// 80 x NB ... 160 registers), so every weight fragment it loads feeds 4 NB MFMAs.
+//   backward (dgrad): the same chain with W^T (transposed once into the workspace) and the ReLU masks out > 0 (torch's threshold_backward);
+//   it writes the masked layer gradients g3 [n, d], g2 [n, 2d], g1 [n, 5d] and g_x [n, d].
+//   backward (wgrad): gW_l = g_l^T h_{l-1}, gb_l = sum_r g_l[r]: per-chunk partials (a fixed row split that depends on n alone) in the workspace,
+//   summed in a fixed order by ngcf_wgrad_fold_kernel -- no float atomics, bit-identical from run to run.
+// ================================================================================================
+template <int D> struct NcfNB { static constexpr int value = D >= 128 ? 1 : (D == 64 ? 2 : 4); };
+constexpr int kNcfChunkRows = 64, kNcfMaxChunks = 128;
+
+// out[nb][m] (C layout of output tile m for row tile nb) = W [O, K] applied to in (B layout); RELU: + bias, relu.  The weight fragments are
+// loaded kNcfPrefetch steps ahead into a small ring, and a scheduling barrier closes every step: left to itself the scheduler hoists all
+// (O / 16) (K / 16) fragment loads of a fully unrolled layer and spills.
+constexpr int kNcfPrefetch = 4;
+template <int O, int K, int NB, bool RELU>
+__device__ __forceinline__ void ncf_layer(const float *__restrict__ W, const float *__restrict__ b, const f32x4v (&in)[NB][K / 16], f32x4v (&out)[NB][O / 16],
+                                          int c, int q) {
+    constexpr int G = K / 16, T = (O / 16) * G, PF = kNcfPrefetch < T ? kNcfPrefetch : T;
+    // buffer loads: one 32-bit per-lane offset (row c, k-quad q) and the step's offset as a constant -- flat loads would keep a 64-bit
+    // address per unrolled step alive
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(W), (short)0, O * K * 4, 0x00020000);
+    const int voff = (c * K + 4 * q) * 4;
+    auto wload = [&](int s) {
+        return __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, (16 * (s / G) * K + 16 * (s % G)) * 4, 0));
+    };
+    f32x4v wb[PF];
+#pragma unroll
+    for (int s = 0; s < PF; ++s) wb[s] = wload(s);
+#pragma unroll
+    for (int m = 0; m < O / 16; ++m) {
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) out[nb][m] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int s = m * G + g;
+            const f32x4v w = wb[s % PF];
+            if (s + PF < T) wb[s % PF] = wload(s + PF);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) out[nb][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[j], in[nb][g][j], out[nb][m], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (RELU) {
+            const f32x4v bb = *reinterpret_cast<const f32x4v *>(b + 16 * m + 4 * q);
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { const float z = out[nb][m][i] + bb[i]; out[nb][m][i] = z > 0.f ? z : 0.f; }
+        }
+    }
+}
+
+template <int T, int NB>
+__device__ __forceinline__ void ncf_store(float *__restrict__ dst, long long ld, const long long (&row)[NB], const bool (&rv)[NB], const f32x4v (&v)[NB][T], int q) {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+        if (rv[nb])
+#pragma unroll
+            for (int m = 0; m < T; ++m) *reinterpret_cast<f32x4v *>(dst + row[nb] * ld + 16 * m + 4 * q) = v[nb][m];
+}
+
+// rows form: rows != NULL (x = mlp[rows[r]], mf row = mf[rows[r]]) and h1 / h2 != NULL (saved for backward); table form: rows = h1 = h2 = NULL
+template <int D>
+__global__ __launch_bounds__(kBlock) void ncf_tower_fwd_kernel(const float *__restrict__ mf, const float *__restrict__ mlp, const int32_t *__restrict__ rows, long long n,
+                                                               const float *__restrict__ W0, const float *__restrict__ b0, const float *__restrict__ W1,
+                                                               const float *__restrict__ b1, const float *__restrict__ W2, const float *__restrict__ b2,
+                                                               float *__restrict__ out, float *__restrict__ h1s, float *__restrict__ h2s) {
+    constexpr int NB = NcfNB<D>::value, RW = 16 * NB;
+    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
+    const long long n_w = (n + RW - 1) / RW;
+    for (long long w = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); w < n_w; w += (long long)gridDim.x * kWavesPerBlock) {
+        long long row[NB], src[NB];
+        bool rv[NB];
+        f32x4v x[NB][D / 16];
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+            row[nb] = w * RW + 16 * nb + c;
+            rv[nb] = row[nb] < n;
+            src[nb] = rv[nb] ? (rows ? (long long)rows[row[nb]] : row[nb]) : 0;
+#pragma unroll
+            for (int g = 0; g < D / 16; ++g) {
+                x[nb][g] = rv[nb] ? *reinterpret_cast<const f32x4v *>(mlp + src[nb] * D + 16 * g + 4 * q) : (f32x4v){0.f, 0.f, 0.f, 0.f};
+                if (rv[nb]) *reinterpret_cast<f32x4v *>(out + row[nb] * 2 * D + 16 * g + 4 * q) = *reinterpret_cast<const f32x4v *>(mf + src[nb] * D + 16 * g + 4 * q);
+            }
+        }
+        f32x4v h1[NB][5 * D / 16];
+        ncf_layer<5 * D, D, NB, true>(W0, b0, x, h1, c, q);
+        if (h1s) ncf_store<5 * D / 16, NB>(h1s, 5 * D, row, rv, h1, q);
+        f32x4v h2[NB][2 * D / 16];
+        ncf_layer<2 * D, 5 * D, NB, true>(W1, b1, h1, h2, c, q);
+        if (h2s) ncf_store<2 * D / 16, NB>(h2s, 2 * D, row, rv, h2, q);
+        ncf_layer<D, 2 * D, NB, true>(W2, b2, h2, x, c, q);
+        ncf_store<D / 16, NB>(out + D, 2 * D, row, rv, x, q);
+    }
+}
+
+template <int T, int NB>
+__device__ __forceinline__ void ncf_mask(f32x4v (&g)[NB][T], const float *__restrict__ h, long long ld, const long long (&row)[NB], const bool (&rv)[NB], int q) {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+        for (int m = 0; m < T; ++m) {
+            const f32x4v a = rv[nb] ? *reinterpret_cast<const f32x4v *>(h + row[nb] * ld + 16 * m + 4 * q) : (f32x4v){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) g[nb][m][i] = a[i] > 0.f ? g[nb][m][i] : 0.f;
+        }
+}
+
+// gOut / Out: [n, 2 D] (the tower half, columns D .. 2 D, is read); WT0 [D][5 D], WT1 [5 D][2 D], WT2 [2 D][D]
+template <int D>
+__global__ __launch_bounds__(kBlock) void ncf_tower_dgrad_kernel(const float *__restrict__ gOut, const float *__restrict__ Out, const float *__restrict__ h1s,
+                                                                 const float *__restrict__ h2s, long long n, const float *__restrict__ WT0,
+                                                                 const float *__restrict__ WT1, const float *__restrict__ WT2, float *__restrict__ g3s,
+                                                                 float *__restrict__ g2s, float *__restrict__ g1s, float *__restrict__ gx) {
+    constexpr int NB = NcfNB<D>::value, RW = 16 * NB;
+    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
+    const long long n_w = (n + RW - 1) / RW;
+    for (long long w = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); w < n_w; w += (long long)gridDim.x * kWavesPerBlock) {
+        long long row[NB];
+        bool rv[NB];
+        f32x4v g3[NB][D / 16];
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+            row[nb] = w * RW + 16 * nb + c;
+            rv[nb] = row[nb] < n;
+#pragma unroll
+            for (int g = 0; g < D / 16; ++g)
+                g3[nb][g] = rv[nb] ? *reinterpret_cast<const f32x4v *>(gOut + row[nb] * 2 * D + D + 16 * g + 4 * q) : (f32x4v){0.f, 0.f, 0.f, 0.f};
+        }
+        ncf_mask<D / 16, NB>(g3, Out + D, 2 * D, row, rv, q);
+        ncf_store<D / 16, NB>(g3s, D, row, rv, g3, q);
+        f32x4v g2[NB][2 * D / 16];
+        ncf_layer<2 * D, D, NB, false>(WT2, nullptr, g3, g2, c, q);
+        ncf_mask<2 * D / 16, NB>(g2, h2s, 2 * D, row, rv, q);
+        ncf_store<2 * D / 16, NB>(g2s, 2 * D, row, rv, g2, q);
+        f32x4v g1[NB][5 * D / 16];
+        ncf_layer<5 * D, 2 * D, NB, false>(WT1, nullptr, g2, g1, c, q);
+        ncf_mask<5 * D / 16, NB>(g1, h1s, 5 * D, row, rv, q);
+        ncf_store<5 * D / 16, NB>(g1s, 5 * D, row, rv, g1, q);
+        ncf_layer<D, 5 * D, NB, false>(WT0, nullptr, g1, g3, c, q);
+        ncf_store<D / 16, NB>(gx, D, row, rv, g3, q);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void transpose_f32_kernel(const float *__restrict__ A, int R, int Cn, float *__restrict__ At) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t < R * Cn) { const int r = t / Cn, cc = t - r * Cn; At[(size_t)cc * R + r] = A[t]; }
+}
+
+// One layer's weight-gradient work: gW [O, K] = G^T H over the rows of a chunk, gb [O] = column sums of G.
+struct NcfWgradLayer {
+    const float *G;                 // [n, O]
+    const float *H;                 // [n_src, K]; row r reads H[idx ? idx[r] : r]
+    const int32_t *idx;
+    int O, K, n_wt;                 // n_wt = (O / 16) * ceil(K / 64): 16 x 64 output blocks; then ceil(O / 64) bias strips
+    long long offW, offb;           // offsets of gW and gb in a partial (floats)
+};
+struct NcfWgradArgs {
+    NcfWgradLayer L[3];
+    int items[4];                   // prefix sums of the layers' work items
+    long long n, chunk;
+    int P;                          // floats per partial
+    float *part;                    // [n_chunks][P]
+};
+
+// grid (n_chunks, ceil(items / 4)), one work item per wave: a 16 x 64 block of one gW (4 accumulators, A fragment reused 4 times) or a 64-column
+// strip of one gb, over the chunk's rows in ascending order
+__global__ __launch_bounds__(kBlock) void ncf_wgrad_kernel(NcfWgradArgs a) {
+    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
+    int it = blockIdx.y * kWavesPerBlock + (threadIdx.x >> 6);
+    if (it >= a.items[3]) return;
+    int l = 0;
+    while (it >= a.items[l + 1]) ++l;
+    it -= a.items[l];
+    const NcfWgradLayer &L = a.L[l];
+    const long long r0 = (long long)blockIdx.x * a.chunk, r1 = r0 + a.chunk < a.n ? r0 + a.chunk : a.n;
+    float *dst = a.part + (size_t)blockIdx.x * a.P;
+    if (it < L.n_wt) {
+        const int kb = (L.K + 63) / 64, mo = it / kb, k0 = (it - mo * kb) * 64;
+        f32x4v acc[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+        for (long long r = r0; r < r1; r += 4) {
+            const long long row = r + q;
+            const bool rv = row < r1;
+            const float av = rv ? L.G[row * L.O + 16 * mo + c] : 0.f;
+            const float *h = L.H + (rv ? (L.idx ? (long long)L.idx[row] : row) : 0) * L.K;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int k = k0 + 16 * t + c;
+                const float bv = (rv && k0 + 16 * t < L.K) ? h[k] : 0.f;
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[t], 0, 0, 0);
+            }
+        }
+        // C layout: acc[t][i] = gW[16 mo + 4 q + i][k0 + 16 t + c]
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (k0 + 16 * t < L.K)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dst[L.offW + (long long)(16 * mo + 4 * q + i) * L.K + k0 + 16 * t + c] = acc[t][i];
+    } else {
+        const int o = (it - L.n_wt) * 64 + lane;
+        if (o >= L.O) return;
+        float s = 0.f;
+        for (long long r = r0; r < r1; ++r) s += L.G[r * L.O + o];
+        dst[L.offb + o] = s;
+    }
+}
+
+// ================================================================================================
+// WRMF loss (util/loss.py:11-15 wrmf_loss + :25-29 l2_reg_loss, as recommender/WRMF.py:42-43 adds them): SUM over the batch of
+// w (<u,p> - 1)^2 + <u,n>^2, plus reg (||U_b||_F + ||P_b||_F).  Same gathers, ordered backward and ownership scan as BPR + L2 above.
+// workspace layout (floats): gp[B] | terms[B] | uu[B] | pp[B] | gn[B]   (gp = 2 w (<u,p> - 1), gn = 2 <u,n>)
+// ================================================================================================
+__global__ __launch_bounds__(kBlock) void wrmf_fwd_kernel(const float *__restrict__ emb, int d, long long item_off, const int32_t *__restrict__ ui,
+                                                          const int32_t *__restrict__ pi, const int32_t *__restrict__ ni, int B, float pos_weight, float *__restrict__ ws) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const float *u = emb + (size_t)ui[b] * d, *p = emb + (size_t)(item_off + pi[b]) * d, *n = emb + (size_t)(item_off + ni[b]) * d;
+    float ps = 0.f, ns = 0.f, uu = 0.f, pp = 0.f;
+    for (int k = lane; k < d; k += kWave) {
+        const float uk = u[k], pk = p[k], nk = n[k];
+        ps = fmaf(uk, pk, ps); ns = fmaf(uk, nk, ns); uu = fmaf(uk, uk, uu); pp = fmaf(pk, pk, pp);
+    }
+    ps = wave_sum(ps); ns = wave_sum(ns); uu = wave_sum(uu); pp = wave_sum(pp);
+    if (lane == 0) {
+        const float e = ps - 1.0f;
+        ws[b] = 2.0f * pos_weight * e;
+        ws[B + b] = pos_weight * (e * e) + ns * ns;
+        ws[2 * B + b] = uu;
+        ws[3 * B + b] = pp;
+        ws[4 * B + b] = 2.0f * ns;
+    }
+}
+
+// single block, fixed-order tree: out[0] = sum of the terms (not a mean), out[1] = reg (||U_b|| + ||P_b||), out[2..3] = the two norms
+__global__ __launch_bounds__(kBlock) void wrmf_finalize_kernel(int B, float reg, const float *__restrict__ ws, float *__restrict__ out) {
+    __shared__ float sh[3][kBlock];
+    float a = 0.f, b = 0.f, c = 0.f;
+    for (int i = threadIdx.x; i < B; i += kBlock) { a += ws[B + i]; b += ws[2 * B + i]; c += ws[3 * B + i]; }
+    sh[0][threadIdx.x] = a; sh[1][threadIdx.x] = b; sh[2][threadIdx.x] = c;
+    __syncthreads();
+    for (int s = kBlock / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            sh[0][threadIdx.x] += sh[0][threadIdx.x + s]; sh[1][threadIdx.x] += sh[1][threadIdx.x + s]; sh[2][threadIdx.x] += sh[2][threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float nu = sqrtf(sh[1][0]), np_ = sqrtf(sh[2][0]);
+        out[0] = sh[0][0];
+        out[1] = reg * (nu + np_);
+        out[2] = nu;
+        out[3] = np_;
+    }
+}
+
+// Backward into the rows of G: contributions numbered as in bpr_bwd_kernel (t = b user, B + b positive, 2 B + b negative), accumulated in that
+// order by the row's owner wave (ordered_scan_lds), no float atomics.
+__global__ __launch_bounds__(kBlock) void wrmf_bwd_kernel(const float *__restrict__ emb, int d, long long item_off, const int32_t *__restrict__ ui,
+                                                          const int32_t *__restrict__ pi, const int32_t *__restrict__ ni, int B, float reg, float upstream,
+                                                          const float *__restrict__ ws, const float *__restrict__ out, float *__restrict__ G, int c0, int c1,
+                                                          int distinct) {
+    extern __shared__ int32_t srows[];
+    const int lane = threadIdx.x & 63;
+    const int t = c0 + blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+#define ARL_ROWOF_WRMF(j) ((j) < B ? (long long)ui[j] : ((j) < 2 * B ? item_off + pi[(j) - B] : item_off + ni[(j) - 2 * B]))
+    if (!distinct) stage_rows(srows, c0, c1, [&](int j) { return ARL_ROWOF_WRMF(j); });
+    if (t >= c1) return;
+    const int row = (int)ARL_ROWOF_WRMF(t);
+    const float cu = out[2] > 0.f ? upstream * reg / out[2] : 0.f, cp = out[3] > 0.f ? upstream * reg / out[3] : 0.f;
+    float *o = G + (size_t)row * d;
+    const float *own = emb + (size_t)row * d;
+    for (int k0 = 0; k0 < d; k0 += 256) {
+        float acc[4], mine[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { const int k = k0 + 64 * i + lane; acc[i] = k < d ? o[k] : 0.f; mine[i] = k < d ? own[k] : 0.f; }
+        auto term = [&](int tt) {
+            const int kind = tt / B, b = tt - kind * B;
+            const float gp = ws[b] * upstream, gn = ws[4 * B + b] * upstream;
+            const float *x = emb + (size_t)(kind == 0 ? item_off + pi[b] : (long long)ui[b]) * d;   // positive row (user term) / user row (item terms)
+            const float *y = emb + (size_t)(item_off + ni[b]) * d;                                // negative row (user term only)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int k = k0 + 64 * i + lane;
+                if (k < d) {
+                    float c;
+                    if (kind == 0) c = fmaf(gp, x[k], fmaf(gn, y[k], cu * mine[i]));
+                    else if (kind == 1) c = fmaf(gp, x[k], cp * mine[i]);
+                    else c = gn * x[k];
+                    acc[i] = __fadd_rn(acc[i], c);
+                }
+            }
+        };
+        if (distinct) term(t);
+        else if (!ordered_scan_lds(srows, c0, c1, t, row, lane, term)) return;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { const int k = k0 + 64 * i + lane; if (k < d) o[k] = acc[i]; }
+    }
+#undef ARL_ROWOF_WRMF
+}
+
+// ================================================================================================
 // SimGCL perturbation (recommender/SimGCL.py:203-205)
 // ================================================================================================
 __global__ __launch_bounds__(kBlock) void simgcl_perturb_kernel(float *__restrict__ E, const float *__restrict__ noise, int n, int d, float eps) {
@@ -5229,5 +5541,119 @@ int arl_topn_project_rows_f32(const float *M, int64_t rows, int64_t cols, int64_
     ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
+
+static int ncf_tower_args(int64_t n, int64_t d) {
+    if (n < 0 || n > 0x7fffffffll) return ARL_E_RANGE;
+    if (d != 16 && d != 32 && d != 64 && d != 128) return ARL_E_DIM;
+    return ARL_OK;
+}
+
+static unsigned ncf_tower_grid(int64_t n, int64_t d) {
+    const int64_t rw = 16 * (d >= 128 ? 1 : (d == 64 ? 2 : 4));
+    const int64_t waves = (n + rw - 1) / rw, want = (waves + kWavesPerBlock - 1) / kWavesPerBlock, cap = 4096;
+    return (unsigned)(want < cap ? want : cap);
+}
+
+int arl_ncf_tower_fwd_f32(const float *mf, const float *mlp, const int32_t *rows, int64_t n, int64_t d, const float *W0, const float *b0,
+                          const float *W1, const float *b1, const float *W2, const float *b2, float *out, float *h1, float *h2, arl_stream_t stream) {
+    if (!mf || !mlp || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !out) return ARL_E_NULL;
+    if ((h1 == nullptr) != (h2 == nullptr)) return ARL_E_ARG;
+    const int rc = ncf_tower_args(n, d);
+    if (rc != ARL_OK) return rc;
+    if (n == 0) return ARL_OK;
+    const unsigned grid = ncf_tower_grid(n, d);
+#define ARL_NCF_FWD(DV) hipLaunchKernelGGL((ncf_tower_fwd_kernel<DV>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, mf, mlp, rows, (long long)n, \
+                                           W0, b0, W1, b1, W2, b2, out, h1, h2)
+    if (d == 16) ARL_NCF_FWD(16); else if (d == 32) ARL_NCF_FWD(32); else if (d == 64) ARL_NCF_FWD(64); else ARL_NCF_FWD(128);
+#undef ARL_NCF_FWD
+    ARL_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
+static int64_t ncf_chunks(int64_t n) {
+    const int64_t c = (n + kNcfChunkRows - 1) / kNcfChunkRows;
+    return c < 1 ? 1 : (c < kNcfMaxChunks ? c : kNcfMaxChunks);
+}
+
+int64_t arl_ncf_tower_bwd_workspace_bytes(int64_t n, int64_t d) {
+    if (n < 0 || d <= 0) return 0;
+    const int64_t P = 17 * d * d + 8 * d;
+    return (int64_t)sizeof(float) * (17 * d * d + 8 * d * n + ncf_chunks(n) * P);
+}
+
+int arl_ncf_tower_bwd_f32(const float *g_out, const float *out, const float *h1, const float *h2, const float *mlp, const int32_t *rows, int64_t n,
+                          int64_t d, const float *W0, const float *W1, const float *W2, float *g_mlp_rows, float *g_params, void *workspace,
+                          arl_stream_t stream) {
+    if (!g_out || !out || !h1 || !h2 || !mlp || !W0 || !W1 || !W2 || !g_mlp_rows || !g_params || !workspace) return ARL_E_NULL;
+    const int rc = ncf_tower_args(n, d);
+    if (rc != ARL_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t P = 17 * d * d + 8 * d;
+    if (n == 0) { hipError_t e = hipMemsetAsync(g_params, 0, sizeof(float) * P, st); return e == hipSuccess ? ARL_OK : (int)e; }
+    float *WT0 = (float *)workspace, *WT1 = WT0 + 5 * d * d, *WT2 = WT1 + 10 * d * d;
+    float *g3 = WT2 + 2 * d * d, *g2 = g3 + n * d, *g1 = g2 + 2 * n * d, *part = g1 + 5 * n * d;
+    const float *Ws[3] = {W0, W1, W2};
+    float *WTs[3] = {WT0, WT1, WT2};
+    const int Rs[3] = {(int)(5 * d), (int)(2 * d), (int)d}, Cs[3] = {(int)d, (int)(5 * d), (int)(2 * d)};
+    for (int l = 0; l < 3; ++l) {
+        hipLaunchKernelGGL(transpose_f32_kernel, dim3((unsigned)((Rs[l] * Cs[l] + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, Ws[l], Rs[l], Cs[l], WTs[l]);
+        ARL_LAUNCH_CHECK();
+    }
+    const unsigned grid = ncf_tower_grid(n, d);
+#define ARL_NCF_DG(DV) hipLaunchKernelGGL((ncf_tower_dgrad_kernel<DV>), dim3(grid), dim3(kBlock), 0, st, g_out, out, h1, h2, (long long)n, WT0, WT1, WT2, \
+                                          g3, g2, g1, g_mlp_rows)
+    if (d == 16) ARL_NCF_DG(16); else if (d == 32) ARL_NCF_DG(32); else if (d == 64) ARL_NCF_DG(64); else ARL_NCF_DG(128);
+#undef ARL_NCF_DG
+    ARL_LAUNCH_CHECK();
+    // weight / bias partials: layer l's gW = G^T H, G = the masked gradient of its output, H = its input (rows of the MLP table for layer 0)
+    const int64_t nc = ncf_chunks(n);
+    NcfWgradArgs a;
+    const float *Gs[3] = {g1, g2, g3}, *Hs[3] = {mlp, h1, h2};
+    long long off = 0;
+    a.items[0] = 0;
+    for (int l = 0; l < 3; ++l) {
+        NcfWgradLayer &L = a.L[l];
+        L.G = Gs[l]; L.H = Hs[l]; L.idx = l == 0 ? rows : nullptr;
+        L.O = Rs[l]; L.K = Cs[l];
+        L.n_wt = (L.O / 16) * ((L.K + 63) / 64);
+        L.offW = off; off += (long long)L.O * L.K;
+        L.offb = off; off += L.O;
+        a.items[l + 1] = a.items[l] + L.n_wt + (L.O + 63) / 64;
+    }
+    a.n = n; a.chunk = (n + nc - 1) / nc; a.P = (int)P; a.part = part;
+    hipLaunchKernelGGL(ncf_wgrad_kernel, dim3((unsigned)nc, (unsigned)((a.items[3] + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, a);
+    ARL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ngcf_wgrad_fold_kernel, dim3((unsigned)((P + 15) / 16)), dim3(kBlock), 0, st, part, (int)nc, (int)P, g_params);
+    ARL_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
+int64_t arl_wrmf_l2_workspace_bytes(int64_t B) { return B < 0 ? 0 : (int64_t)sizeof(float) * 5 * B; }
+
+int arl_wrmf_l2_fwd_bwd_f32(const float *emb, int64_t d, int64_t item_off, const int32_t *u, const int32_t *p, const int32_t *n, int64_t B,
+                            float pos_weight, float reg, float upstream, float *loss_out, float *G, void *workspace, int32_t distinct_rows,
+                            arl_stream_t stream) {
+    if (!emb || !u || !p || !n || !loss_out || !workspace) return ARL_E_NULL;
+    if (d <= 0 || B <= 0 || item_off < 0) return ARL_E_ARG;
+    if (B > 0x7fffffffll / 5 || d > 0x7fffffffll) return ARL_E_RANGE;
+    hipStream_t st = (hipStream_t)stream;
+    float *ws = (float *)workspace;
+    hipLaunchKernelGGL(wrmf_fwd_kernel, dim3((unsigned)((B + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, emb, (int)d, (long long)item_off,
+                       u, p, n, (int)B, pos_weight, ws);
+    ARL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(wrmf_finalize_kernel, dim3(1), dim3(kBlock), 0, st, (int)B, reg, ws, loss_out);
+    ARL_LAUNCH_CHECK();
+    if (!G) return ARL_OK;
+    const int64_t total = 3 * B;
+    const int distinct = distinct_rows != 0;
+    for (int64_t c0 = 0; c0 < total; c0 += kOrderedWindow) {
+        const int64_t c1 = c0 + kOrderedWindow < total ? c0 + kOrderedWindow : total;
+        hipLaunchKernelGGL(wrmf_bwd_kernel, dim3((unsigned)((c1 - c0 + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), distinct ? 0 : (size_t)(c1 - c0) * 4, st,
+                           emb, (int)d, (long long)item_off, u, p, n, (int)B, reg, upstream, ws, loss_out, G, (int)c0, (int)c1, distinct);
+        ARL_LAUNCH_CHECK();
+    }
+    return ARL_OK;
+}
+
 
 }  // extern "C"

@@ -1491,6 +1491,106 @@ def ngcf_dense_bwd(gOut, Out, P, E, Wcat, slope=0.01):
     return gP, gE, gW
 
 
+NCF_TOWER_WIDTHS = NGCF_DENSE_WIDTHS
+
+
+def _ncf_weights(W, d):
+    W0, b0, W1, b1, W2, b2 = W
+    for t, nm, shp in ((W0, 'W0', (5 * d, d)), (b0, 'b0', (5 * d,)), (W1, 'W1', (2 * d, 5 * d)), (b1, 'b1', (2 * d,)), (W2, 'W2', (d, 2 * d)),
+                       (b2, 'b2', (d,))):
+        _dev(t, torch.float32, nm)
+        if tuple(t.shape) != shp:
+            raise ValueError('ncf_tower: %s has shape %s, expected %s (nn.Linear layout)' % (nm, tuple(t.shape), shp))
+
+
+def _ncf_rows(rows, N, check_range):
+    if rows is None:
+        return None
+    _dev(rows, torch.int32, 'rows', 1)
+    if check_range and rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= N):
+        raise IndexError('ncf_tower: row index out of range')
+    return rows
+
+
+def ncf_tower_fwd(mf, mlp, W, rows=None, save_activations=None, check_range=True):
+    """NCF scored rows [mf[s] | relu(W2 relu(W1 relu(W0 mlp[s] + b0) + b1) + b2)] as [n, 2d], one fused kernel (exact fp32 MFMA).
+    W = (W0, b0, W1, b1, W2, b2) in nn.Linear layout.  rows (int32, may repeat): the rows form over s = rows[r], which by default also returns
+    the activations backward needs: (out, h1 [n, 5d], h2 [n, 2d]).  rows=None: the table form over every row, returns out alone."""
+    _dev(mf, torch.float32, 'mf', 2); _dev(mlp, torch.float32, 'mlp', 2)
+    N, d = mlp.shape
+    if mf.shape != mlp.shape or d not in NCF_TOWER_WIDTHS:
+        raise ValueError('ncf_tower_fwd: mf, mlp [N, d] with d in %s' % (NCF_TOWER_WIDTHS,))
+    _ncf_weights(W, d)
+    rows = _ncf_rows(rows, N, check_range)
+    save = (rows is not None) if save_activations is None else bool(save_activations)
+    n = N if rows is None else rows.numel()
+    out = torch.empty(n, 2 * d, dtype=torch.float32, device=mlp.device)
+    h1 = torch.empty(n, 5 * d, dtype=torch.float32, device=mlp.device) if save else None
+    h2 = torch.empty(n, 2 * d, dtype=torch.float32, device=mlp.device) if save else None
+    check(_lib.lib().arl_ncf_tower_fwd_f32(_ptr(mf), _ptr(mlp), _ptr(rows), n, d, *[_ptr(t) for t in W], _ptr(out), _ptr(h1), _ptr(h2), _stream()),
+          'arl_ncf_tower_fwd_f32')
+    return (out, h1, h2) if save else out
+
+
+def ncf_tower_bwd(g_out, out, h1, h2, mlp, W, rows=None, check_range=True):
+    """Backward of ncf_tower_fwd's rows form: from g_out [n, 2d] (its tower half is read) returns (g_mlp_rows [n, d] in row order -- duplicates
+    not summed --, [gW0, gb0, gW1, gb1, gW2, gb2]).  Weight and bias sums are deterministic (fixed-order reduction, no float atomics)."""
+    _dev(mlp, torch.float32, 'mlp', 2)
+    N, d = mlp.shape
+    if d not in NCF_TOWER_WIDTHS:
+        raise ValueError('ncf_tower_bwd: d in %s' % (NCF_TOWER_WIDTHS,))
+    _ncf_weights(W, d)
+    rows = _ncf_rows(rows, N, check_range)
+    n = N if rows is None else rows.numel()
+    for t, nm, w in ((g_out, 'g_out', 2 * d), (out, 'out', 2 * d), (h1, 'h1', 5 * d), (h2, 'h2', 2 * d)):
+        _dev(t, torch.float32, nm, 2)
+        if tuple(t.shape) != (n, w):
+            raise ValueError('ncf_tower_bwd: %s has shape %s, expected %s' % (nm, tuple(t.shape), (n, w)))
+    L = _lib.lib()
+    g_rows = torch.empty(n, d, dtype=torch.float32, device=mlp.device)
+    flat = torch.empty(17 * d * d + 8 * d, dtype=torch.float32, device=mlp.device)
+    ws = torch.empty(max(1, L.arl_ncf_tower_bwd_workspace_bytes(n, d) // 4), dtype=torch.float32, device=mlp.device)
+    W0, _, W1, _, W2, _ = W
+    check(L.arl_ncf_tower_bwd_f32(_ptr(g_out), _ptr(out), _ptr(h1), _ptr(h2), _ptr(mlp), _ptr(rows), n, d, _ptr(W0), _ptr(W1), _ptr(W2), _ptr(g_rows),
+                                  _ptr(flat), _ptr(ws), _stream()), 'arl_ncf_tower_bwd_f32')
+    grads, off = [], 0
+    for shp in ((5 * d, d), (5 * d,), (2 * d, 5 * d), (2 * d,), (d, 2 * d), (d,)):
+        k = int(np.prod(shp))
+        grads.append(flat[off:off + k].view(shp))
+        off += k
+    return g_rows, grads
+
+
+def wrmf_l2_fwd_bwd(emb, item_off, u, p, n, reg, pos_weight=20.0, G=None, upstream=1.0, workspace=None, loss_out=None, check_range=True,
+                    distinct_rows=False):
+    """WRMF + L2 on rows gathered from the combined table; returns loss_out = [sum_b w (<u,p>-1)^2 + <u,n>^2, reg_term, ||U_b||, ||P_b||]
+    (device; the WRMF term is a SUM over the batch).  If G is given the gradient w.r.t. `emb` rows is added into it with bpr_l2_fwd_bwd's
+    duplicate order and determinism."""
+    _dev(emb, torch.float32, 'emb', 2)
+    N, d = emb.shape
+    B = u.numel()
+    for t, nm in ((u, 'u'), (p, 'p'), (n, 'n')):
+        _check_idx(t, nm, N, B)
+    if B == 0:
+        raise ValueError('wrmf_l2: empty batch')
+    if check_range:
+        mx = torch.stack([u.max(), p.max(), n.max(), -u.min(), -p.min(), -n.min()]).tolist()
+        if mx[0] >= N or max(mx[1], mx[2]) + item_off >= N or max(mx[3:]) > 0:
+            raise IndexError('wrmf_l2: batch index out of range')
+    if G is not None:
+        _dev(G, torch.float32, 'G', 2)
+        if G.shape != emb.shape:
+            raise ValueError('wrmf_l2: G shape mismatch')
+    need = _lib.lib().arl_wrmf_l2_workspace_bytes(B)
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=emb.device)
+    if loss_out is None:
+        loss_out = torch.empty(4, dtype=torch.float32, device=emb.device)
+    check(_lib.lib().arl_wrmf_l2_fwd_bwd_f32(_ptr(emb), d, item_off, _ptr(u), _ptr(p), _ptr(n), B, float(pos_weight), float(reg), float(upstream),
+                                             _ptr(loss_out), _ptr(G), _ptr(workspace), 1 if distinct_rows else 0, _stream()), 'arl_wrmf_l2_fwd_bwd_f32')
+    return loss_out
+
+
 def bpr_l2_partial(emb, item_off, u, p, n, B_global, workspace, sums_out):
     """Per-sample BPR coefficients (into `workspace`) + local sums [sum loss terms, sum|u|^2, sum|p|^2] (into sums_out)."""
     _dev(emb, torch.float32, 'emb', 2); _dev(sums_out, torch.float32, 'sums_out', 1); _dev(workspace, torch.float32, 'workspace', 1)

@@ -398,6 +398,18 @@ class Recommender:
     def _extra_loss(self, model, user_idx, pos_idx):
         return None
 
+    def _batch_loss(self, user_emb, pos_item_emb, neg_item_emb, reg):
+        """The step's main loss on the gathered rows: BPR + L2 (every model but WRMF, which overrides it)."""
+        return bpr_l2_loss(user_emb, pos_item_emb, neg_item_emb, reg)
+
+    def _embgrad_begin(self, model):
+        self.usergrad = torch.zeros((self.data.user_num, self.args.emb_size), device=DEVICE)
+        self.itemgrad = torch.zeros((self.data.item_num, self.args.emb_size), device=DEVICE)
+
+    def _embgrad_accumulate(self, model):
+        self.usergrad += model.embedding_dict['user_emb'].grad
+        self.itemgrad += model.embedding_dict['item_emb'].grad
+
     def _on_epoch_start(self, model):
         pass
 
@@ -434,8 +446,7 @@ class Recommender:
             self.Matgrad = torch.zeros(adj.values.numel(), dtype=torch.float32, device=DEVICE)
         if requires_embgrad:
             model.requires_grad = True
-            self.usergrad = torch.zeros((self.data.user_num, self.args.emb_size), device=DEVICE)
-            self.itemgrad = torch.zeros((self.data.item_num, self.args.emb_size), device=DEVICE)
+            self._embgrad_begin(model)
         maxEpoch = Epoch if Epoch else self.args.maxEpoch
         # reference quirk Q4 (attack/White/PGA.py:59-67, DLAttack.py:53-68): an optimizer built on a model that
         # recommender.__init__ has since replaced owns none of the live parameters, so the reference's loop moves
@@ -490,7 +501,7 @@ class Recommender:
                     if adj is not None:
                         rec_user_emb.retain_grad(); rec_item_emb.retain_grad()
                     user_emb, pos_item_emb, neg_item_emb = rec_user_emb[ul], rec_item_emb[pl], rec_item_emb[nl]
-                batch_loss = bpr_l2_loss(user_emb, pos_item_emb, neg_item_emb, self.args.reg * self.l2_scale)
+                batch_loss = self._batch_loss(user_emb, pos_item_emb, neg_item_emb, self.args.reg * self.l2_scale)
                 if self.l2_on_negatives:
                     batch_loss = batch_loss + l2_reg_loss(self.args.reg * self.l2_scale, neg_item_emb)
                 if self.has_extra_loss:
@@ -506,8 +517,7 @@ class Recommender:
                     if maxEpoch - epoch < gradIterationNum:
                         self.Matgrad += adj.values.grad
                 if requires_embgrad and maxEpoch - epoch < gradIterationNum:
-                    self.usergrad += model.embedding_dict['user_emb'].grad
-                    self.itemgrad += model.embedding_dict['item_emb'].grad
+                    self._embgrad_accumulate(model)
                 self._after_backward(model, epoch, maxEpoch, gradIterationNum)
                 optimizer.step()
                 if n % self.print_every == 0:
@@ -604,7 +614,7 @@ class Recommender:
                 continue
             outs = model(True) if self.train_forward_perturbed else model()
             rec_user_emb, rec_item_emb = outs[0], outs[1]
-            loss = bpr_l2_loss(rec_user_emb[u.long()], rec_item_emb[p.long()], rec_item_emb[ng.long()], self.args.reg * self.l2_scale)
+            loss = self._batch_loss(rec_user_emb[u.long()], rec_item_emb[p.long()], rec_item_emb[ng.long()], self.args.reg * self.l2_scale)
             if self.l2_on_negatives:
                 loss = loss + l2_reg_loss(self.args.reg * self.l2_scale, rec_item_emb[ng.long()])
             if self.has_extra_loss:

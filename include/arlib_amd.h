@@ -334,6 +334,40 @@ int64_t arl_ngcf_wgrad_workspace_bytes(int64_t n, int64_t d);
 int arl_ngcf_dense_wgrad_f32(const float *P, const float *E, const float *gZ, int64_t n, int64_t d, float *gW, void *workspace, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * NCF MLP tower -- replaces the tower loop and the two torch.cat of recommender/NCF.py:203-220
+ *   (Linear(d, 5d) -> ReLU -> Linear(5d, 2d) -> ReLU -> Linear(2d, d) -> ReLU, nn.Linear weights [out, in] row-major, biases [out]).
+ * One kernel, exact fp32 on v_mfma_f32_16x16x4_f32, the activations of a row tile kept in registers; d in {16, 32, 64, 128}.
+ *   fwd : out[r] = [mf[s] | tower(mlp[s])] as [n, 2d], s = rows[r] (rows != NULL: rows form, entries may repeat) or s = r (rows == NULL:
+ *         table form over the first n rows).  h1 [n, 5d] and h2 [n, 2d] (both or neither): the ReLU outputs backward needs.
+ *   bwd : from g_out [n, 2d] (its tower half, columns d .. 2d, is read), out, h1, h2 of a rows-form call and the same mlp / rows / weights:
+ *         g_mlp_rows [n, d] = the gradient of the tower's input rows (in row order; duplicates are NOT summed here), and
+ *         g_params = [gW0 | gb0 | gW1 | gb1 | gW2 | gb2] (17 d^2 + 8 d floats, nn.Linear layouts) summed over the n rows.  ReLU gradient
+ *         out > 0 (torch's threshold_backward).  The sums run over per-chunk partials (a fixed split of the rows that depends on n alone)
+ *         folded in a fixed order: no float atomics, bit-identical from run to run.
+ * workspace: arl_ncf_tower_bwd_workspace_bytes(n, d) bytes of device memory.
+ * ---------------------------------------------------------------------------------------------- */
+int arl_ncf_tower_fwd_f32(const float *mf, const float *mlp, const int32_t *rows, int64_t n, int64_t d, const float *W0, const float *b0,
+                          const float *W1, const float *b1, const float *W2, const float *b2, float *out, float *h1, float *h2, arl_stream_t stream);
+int64_t arl_ncf_tower_bwd_workspace_bytes(int64_t n, int64_t d);
+int arl_ncf_tower_bwd_f32(const float *g_out, const float *out, const float *h1, const float *h2, const float *mlp, const int32_t *rows, int64_t n,
+                          int64_t d, const float *W0, const float *W1, const float *W2, float *g_mlp_rows, float *g_params, void *workspace,
+                          arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * WRMF loss + un-squared L2 on gathered rows, forward + backward in one call.
+ * Replaces util/loss.py:11-15 (wrmf_loss), :25-29 (l2_reg_loss), the gathers of recommender/WRMF.py:40-43 and their autograd.
+ *   loss_out[0] = SUM_b  pos_weight (<u,p> - 1)^2 + <u,n>^2   (a sum over the batch, as the reference; not a mean)
+ *   loss_out[1] = reg*(||U_b||_F + ||P_b||_F)   loss_out[2] = ||U_b||_F   loss_out[3] = ||P_b||_F
+ *   G[row] += upstream * d(loss)/d(emb[row]) with the row order, ownership scan and determinism of arl_bpr_l2_fwd_bwd_f32 (no float
+ *   atomics, bit-identical from run to run); G may be NULL; distinct_rows as there.
+ * workspace: arl_wrmf_l2_workspace_bytes(B) bytes of device memory.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t arl_wrmf_l2_workspace_bytes(int64_t B);
+int arl_wrmf_l2_fwd_bwd_f32(const float *emb, int64_t d, int64_t item_off, const int32_t *u, const int32_t *p, const int32_t *n, int64_t B,
+                            float pos_weight, float reg, float upstream, float *loss_out, float *G, void *workspace, int32_t distinct_rows,
+                            arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * White-box attack primitives.
  * ---------------------------------------------------------------------------------------------- */
 /* ------------------------------------------------------------------------------------------------
