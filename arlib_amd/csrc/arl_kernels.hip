@@ -5102,7 +5102,8 @@ int arl_ngcf_dense_wgrad_f32(const float *P, const float *E, const float *gZ, in
 int arl_simgcl_perturb_rng_f32(const float *src, float *dst, int64_t n, int64_t d, const int32_t *row_ids, float eps, uint64_t seed, uint64_t stream_id,
                                arl_stream_t stream) {
     if (!src || !dst) return ARL_E_NULL;
-    if (n < 0 || d <= 0 || d > 256 || n > 0x7fffffffll) return ARL_E_ARG;
+    if (d <= 0 || d > 256) return ARL_E_DIM;
+    if (n < 0 || n > 0x7fffffffll) return ARL_E_ARG;
     if (n == 0) return ARL_OK;
     unsigned long long key = seed ^ (stream_id * 0x9E3779B97F4A7C15ull);          // one hash of (seed, stream) keys the whole call
     key += 0x9E3779B97F4A7C15ull; key = (key ^ (key >> 30)) * 0xBF58476D1CE4E5B9ull; key = (key ^ (key >> 27)) * 0x94D049BB133111EBull; key ^= key >> 31;
@@ -5216,7 +5217,8 @@ int arl_sfa_stage3_f32(const float *X, const float *w, const float *r0, const fl
 int arl_sddmm_rows_dense_f32(const float *dY, const float *X, int64_t d, const int32_t *rows, int64_t n_rows_sel, int64_t col_off, int64_t n_cols,
                              float *out, arl_stream_t stream) {
     if (!dY || !X || !rows || !out) return ARL_E_NULL;
-    if (d <= 0 || d > 256 || n_rows_sel < 0 || n_cols < 0 || col_off < 0) return ARL_E_ARG;
+    if (d <= 0 || d > 256) return ARL_E_DIM;
+    if (n_rows_sel < 0 || n_cols < 0 || col_off < 0) return ARL_E_ARG;
     if (n_cols > 0x7fffffffll || n_rows_sel > 0x7fffffffll) return ARL_E_RANGE;
     if (n_rows_sel == 0 || n_cols == 0) return ARL_OK;
     if (d == 64) {

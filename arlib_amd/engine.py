@@ -56,6 +56,8 @@ class PropagationEngine:
             raise ValueError('n_layers > 0 needs a graph')
         if graph is not None and graph.n_rows != self.N:
             raise ValueError('graph has %d rows, expected U+I=%d' % (graph.n_rows, self.N))
+        if self.L > 0:
+            ops._check_width(self.d, 'PropagationEngine')      # the propagation hops' widths: refused here, before any buffer or launch
         if self.skip0 and self.L < 1:
             raise ValueError('skip_layer0 needs n_layers >= 1')
         if schedule not in ('auto', 'csr', 'blocked'):

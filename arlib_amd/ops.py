@@ -620,14 +620,19 @@ class IncrementalBipartite:
         return bp
 
 
+def _check_width(d, name, multiple_of_4=True):
+    """The embedding widths the row kernels take: 1..256, and a multiple of 4 where they move rows as float4."""
+    if d <= 0 or d > 256 or (multiple_of_4 and d % 4):
+        raise ValueError('%s: embedding size %d unsupported (%s<= 256)' % (name, d, 'multiple of 4, ' if multiple_of_4 else ''))
+
+
 def _check_xy(A, X, name='X', rows=None):
     _dev(X, torch.float32, name, 2)
     want = A.n_rows if rows is None else rows
     if X.shape[0] != want:
         raise ValueError('%s: %d rows, expected %d' % (name, X.shape[0], want))
     d = X.shape[1]
-    if d % 4 or d > 256:
-        raise ValueError('embedding size %d unsupported (multiple of 4, <= 256)' % d)
+    _check_width(d, name)
     if X.device != A.device:
         raise ValueError('%s on %s, graph on %s' % (name, X.device, A.device))
     return d
@@ -991,6 +996,7 @@ def nce_allrows(A, V, tau, want_grad=True, want_dV=True, lse=None):
 def normalize_rows(X):
     """(Y, nrm) = (F.normalize(X, dim=1), max(||X_r||, 1e-12)) in one pass (recommender/NCL.py:98-99)."""
     _dev(X, torch.float32, 'X', 2)
+    _check_width(X.shape[1], 'normalize_rows')
     Y, nrm = torch.empty_like(X), torch.empty(X.shape[0], dtype=torch.float32, device=X.device)
     check(_lib.lib().arl_normalize_rows_f32(_ptr(X), X.shape[0], X.shape[1], _ptr(Y), _ptr(nrm), _stream()), 'arl_normalize_rows_f32')
     return Y, nrm
@@ -1004,6 +1010,7 @@ def normalize_rows_bwd(Y, nrm, dY, scale=1.0, out=None, scale_dev=None):
     _dev(out, torch.float32, 'out', 2)
     if dY.shape != Y.shape or out.shape != Y.shape or nrm.numel() != Y.shape[0]:
         raise ValueError('normalize_rows_bwd: shape mismatch')
+    _check_width(Y.shape[1], 'normalize_rows_bwd')
     if scale_dev is not None:
         _dev(scale_dev, torch.float32, 'scale_dev')
     check(_lib.lib().arl_normalize_rows_bwd_f32(_ptr(Y), _ptr(nrm), _ptr(dY), Y.shape[0], Y.shape[1], float(scale), _ptr(scale_dev), _ptr(out), _stream()), 'arl_normalize_rows_bwd_f32')
@@ -1015,6 +1022,7 @@ def simgcl_perturb_rng(src, eps, seed, stream_id, out=None, row_ids=None):
     SimGCL perturbation (SimGCL.py:203-205) without a noise table or a clone.  out may be src (in place).  row_ids (int32, optional): src holds
     those rows of a larger table; they get the noise of a full-table call with the same (seed, stream_id)."""
     _dev(src, torch.float32, 'src', 2)
+    _check_width(src.shape[1], 'simgcl_perturb_rng', multiple_of_4=False)
     if out is None:
         out = torch.empty_like(src)
     _dev(out, torch.float32, 'out', 2)
@@ -1103,6 +1111,7 @@ def sddmm_rows_dense(dY, X, rows, col_off, n_cols, out=None):
     _dev(dY, torch.float32, 'dY', 2); _dev(X, torch.float32, 'X', 2); _dev(rows, torch.int32, 'rows', 1)
     if dY.shape[1] != X.shape[1] or col_off < 0 or col_off + n_cols > X.shape[0]:
         raise ValueError('sddmm_rows_dense: shape mismatch')
+    _check_width(X.shape[1], 'sddmm_rows_dense', multiple_of_4=False)
     if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= dY.shape[0]):
         raise IndexError('sddmm_rows_dense: row out of range')
     if out is None:
@@ -1121,6 +1130,7 @@ def sddmm_csr(A, dY, X, alpha=1.0, out=None):
     _dev(dY, torch.float32, 'dY', 2); _dev(X, torch.float32, 'X', 2)
     if dY.shape[0] != A.n_rows or dY.shape[1] != X.shape[1] or X.shape[0] < A.n_cols:
         raise ValueError('sddmm_csr: dY [n_rows, d], X [n_cols, d]')
+    _check_width(X.shape[1], 'sddmm_csr')
     if out is None:
         out = torch.zeros(A.col.numel(), dtype=torch.float32, device=X.device)
     _dev(out, torch.float32, 'out', 1)

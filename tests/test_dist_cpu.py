@@ -253,8 +253,8 @@ def test_sharded_clear_step_gloo_matches_single_process_oracle(world, skip0):
     assert rel_err(ret['table'], ref_table) < RTOL
 
 
-def ngcf_problem():
-    U, I, d, _, pairs, E0, batches = small_problem()
+def ngcf_problem(d=16):
+    U, I, d, _, pairs, E0, batches = small_problem(d)
     rng = np.random.default_rng(13)
     L = 2
     W1 = [(rng.standard_normal((d, d)) * 0.3).astype(np.float32) for _ in range(L)]
@@ -289,7 +289,7 @@ def torch_ngcf_steps(U, I, d, L, pairs, E0, batches, W1, W2, reg=1e-4, lr=0.005)
     return E.detach().numpy(), [x.detach().numpy() for x in Ws], losses
 
 
-def _ngcf_worker(rank, world, port, ret):
+def _ngcf_worker(rank, world, port, ret, d=16):
     sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import torch.distributed as dist
     import cpu_kernels_shim as shim
@@ -297,7 +297,7 @@ def _ngcf_worker(rank, world, port, ret):
     os.environ['MASTER_ADDR'] = '127.0.0.1'; os.environ['MASTER_PORT'] = str(port)
     dist.init_process_group('gloo', rank=rank, world_size=world)
     torch.set_num_threads(1)
-    U, I, d, L, pairs, E0, batches, W1, W2 = ngcf_problem()
+    U, I, d, L, pairs, E0, batches, W1, W2 = ngcf_problem(d)
     eng = ShardedPropagationEngine.from_pairs(pairs, U, I, d, L, 1e-4, 0.005, 'cpu', rank, world, torch.from_numpy(E0), kernels=shim)
     eng.init_ngcf(W1, W2)
     losses = []
@@ -314,14 +314,16 @@ def _ngcf_worker(rank, world, port, ret):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize('world', [2, 3])
-def test_sharded_ngcf_steps_gloo_match_torch_autograd_reference(world):
+@pytest.mark.parametrize('world,d', [(2, 16), (3, 16), (2, 12)], ids=['2', '3', '2-d12'])
+def test_sharded_ngcf_steps_gloo_match_torch_autograd_reference(world, d):
     """BASELINE config 5's training step: NGCF on user shards (one hop per layer with its item-row all-reduce, row-local dense part with
-    replicated weights, weight gradients all-reduced) against the reference's layer expression under torch autograd on a dense fp64 graph."""
-    prob = ngcf_problem()
+    replicated weights, weight gradients all-reduced) against the reference's layer expression under torch autograd on a dense fp64 graph.
+    d = 12: the problem builder at a width besides its default."""
+    prob = ngcf_problem(d)
+    assert prob[2] == d and prob[5].shape[1] == d
     ref_table, ref_W, ref_losses = torch_ngcf_steps(*prob)
     ret = mp.Manager().dict()
-    mp.spawn(_ngcf_worker, args=(world, free_port(), ret), nprocs=world, join=True)
+    mp.spawn(_ngcf_worker, args=(world, free_port(), ret, d), nprocs=world, join=True)
     L, d = prob[3], prob[2]
     assert np.allclose(ret['losses'], ref_losses, rtol=RTOL, atol=0)
     assert rel_err(ret['table'], ref_table) < RTOL

@@ -183,7 +183,7 @@ def test_sharded_clear_step_two_ranks_hip_kernels(skip0, comm):
     assert rel_err(ret['table'], ref_table) < RTOL
 
 
-def _ngcf_worker(rank, world, port, ret, comm='staged'):
+def _ngcf_worker(rank, world, port, ret, comm='staged', d=16):
     sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import torch.distributed as dist
     from arlib_amd.dist_engine import ShardedPropagationEngine
@@ -191,7 +191,17 @@ def _ngcf_worker(rank, world, port, ret, comm='staged'):
     os.environ['MASTER_ADDR'] = '127.0.0.1'; os.environ['MASTER_PORT'] = str(port)
     dist.init_process_group('gloo', rank=rank, world_size=world)
     torch.cuda.set_device(0)
-    U, I, d, L, pairs, E0, batches, W1, W2 = ngcf_problem()
+    from arlib_amd import ops
+    calls = {'ngcf_combine': 0, 'ngcf_dense_fwd': 0}                 # which dense branch the step takes (this process only)
+
+    def counted(f, key):
+        def wrapper(*a, **kw):
+            calls[key] += 1
+            return f(*a, **kw)
+        return wrapper
+    for name in calls:
+        setattr(ops, name, counted(getattr(ops, name), name))
+    U, I, d, L, pairs, E0, batches, W1, W2 = ngcf_problem(d)
     eng = ShardedPropagationEngine.from_pairs(pairs, U, I, d, L, 1e-4, 0.005, 'cuda:0', rank, world, torch.from_numpy(E0), comm=_comm(comm))
     eng.init_ngcf(W1, W2)
     losses = []
@@ -201,18 +211,24 @@ def _ngcf_worker(rank, world, port, ret, comm='staged'):
     full = eng.gather_full_table().cpu().numpy()
     if rank == 0:
         ret['table'], ret['losses'], ret['W'] = full, losses, [w.cpu().numpy() for w in eng.W]
+        ret['calls'] = dict(calls)
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize('comm', ['staged', 'deferred'])
-def test_sharded_ngcf_two_ranks_hip_kernels(comm):
-    """BASELINE config 5's training step (NGCF, user-sharded) with the real kernels against torch autograd on a dense fp64 graph."""
+@pytest.mark.parametrize('comm,d', [('staged', 16), ('deferred', 16), ('staged', 12)], ids=['staged', 'deferred', 'staged-d12'])
+def test_sharded_ngcf_two_ranks_hip_kernels(comm, d):
+    """BASELINE config 5's training step (NGCF, user-sharded) with the real kernels against torch autograd on a dense fp64 graph.  d = 12 is
+    outside NGCF_DENSE_WIDTHS: the engine's element-wise branch (ngcf_combine / ngcf_act_ / ngcf_act_bwd / ngcf_combine_bwd + torch.mm)."""
     if not torch.cuda.is_available():
         pytest.fail('GPU tests need a GPU')
+    from arlib_amd import ops
     from test_dist_cpu import ngcf_problem, torch_ngcf_steps
-    prob = ngcf_problem()
+    assert (d in ops.NGCF_DENSE_WIDTHS) == (d == 16)
+    prob = ngcf_problem(d)
     ref_table, ref_W, ref_losses = torch_ngcf_steps(*prob)
-    ret = _spawn(_ngcf_worker, (comm,))
+    ret = _spawn(_ngcf_worker, (comm, d))
+    fused = d in ops.NGCF_DENSE_WIDTHS
+    assert (ret['calls']['ngcf_dense_fwd'] > 0) == fused and (ret['calls']['ngcf_combine'] > 0) == (not fused), ret['calls']
     L, d = prob[3], prob[2]
     assert np.allclose(ret['losses'], ref_losses, rtol=RTOL, atol=0)
     assert rel_err(ret['table'], ref_table) < RTOL
