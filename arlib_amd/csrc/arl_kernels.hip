@@ -2034,6 +2034,105 @@ __global__ __launch_bounds__(kBlock) void simgcl_perturb_rng_kernel(const float 
 }
 
 // ================================================================================================
+// SSL4Rec's contrastive term (recommender/SSL4Rec.py:232-247, util/loss.py:42-49): for the compact batch rows X of one side (users or
+// positive items, duplicates kept), two nn.Dropout(p) views V1 = X * M1 * s, V2 = X * M2 * s (s = 1 / (1 - p)) and InfoNCE(V1, V2, tau).
+// Mask bit of (side, view, position i, column k), sv = 2 * side + view:
+//   injected: bit b = (sv * n + i) * d + k of the packed words, (masks[b >> 5] >> (b & 31)) & 1;
+//   drawn   : u = (splitmix64(key ^ (((sv << 32) + i) * d + k)) >> 40) * 2^-24, kept iff u >= p, with key = the hash of (seed, stream) that
+//             arl_simgcl_perturb_rng_f32 forms.
+__device__ __forceinline__ bool ssl_keep(const uint32_t *__restrict__ masks, unsigned long long key, int sv, int n, int i, int d, int k, float p) {
+    if (masks) {
+        const size_t b = ((size_t)sv * n + i) * d + k;
+        return (masks[b >> 5] >> (b & 31)) & 1u;
+    }
+    const unsigned long long c = (((unsigned long long)sv << 32) + (unsigned long long)i) * (unsigned long long)d + (unsigned long long)k;
+    return (float)(arl_splitmix64(key ^ c) >> 40) * (1.0f / 16777216.0f) >= p;
+}
+
+// one wave per (side, view, position): the dropped, scaled row, normalised (F.normalize: / max(||v||, 1e-12)) -> views[sv][i], nrm[sv][i]
+template <int D>
+__global__ __launch_bounds__(kBlock) void ssl_views_kernel(const float *__restrict__ Xu, const float *__restrict__ Xp, int n, float p, float s,
+                                                            unsigned long long key, const uint32_t *__restrict__ masks, float *__restrict__ views,
+                                                            float *__restrict__ nrm) {
+    constexpr int QN = (D + kWave - 1) / kWave;
+    const int lane = threadIdx.x & 63;
+    const int w = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (w >= 4 * n) return;
+    const int sv = w / n, i = w - sv * n;
+    const float *X = (sv >> 1) ? Xp : Xu;
+    float v[QN], ss = 0.f;
+#pragma unroll
+    for (int q = 0; q < QN; ++q) {
+        const int k = lane + q * kWave;
+        v[q] = 0.f;
+        if (k < D && ssl_keep(masks, key, sv, n, i, D, k, p)) v[q] = X[(size_t)i * D + k] * s;
+        ss = fmaf(v[q], v[q], ss);
+    }
+    ss = wave_sum(ss);
+    const float nr = fmaxf(sqrtf(ss), 1e-12f);
+#pragma unroll
+    for (int q = 0; q < QN; ++q) {
+        const int k = lane + q * kWave;
+        if (k < D) views[(size_t)w * D + k] = v[q] / nr;
+    }
+    if (lane == 0) nrm[w] = nr;
+}
+
+// one wave per (side, position): with a = views[side][0][i], b = views[side][1][i], ga = dA[i] - b, gb = dV[i] - a (dA = sum_j P_ij b_j,
+// dV = sum_j P_ji a_j), the normalisation's backward dVv = (g - y <y, g>) / nrm per view, then
+//   G[i] += c * (M1 ? dV1 : 0) + c * (M2 ? dV2 : 0),  c = upstream * s / (n * tau),   term[side][i] = lse_i - <a, b> / tau
+// (a select, not a product with the mask: an all-dropped row has nrm = 1e-12 and a large dV that must not reach G)
+template <int D>
+__global__ __launch_bounds__(kBlock) void ssl_finish_kernel(const float *__restrict__ views, const float *__restrict__ nrm, const float *__restrict__ dA,
+                                                             const float *__restrict__ dV, const float *__restrict__ lse, int n, int n4, float p, float inv_tau,
+                                                             float c, unsigned long long key, const uint32_t *__restrict__ masks, float *__restrict__ Gu,
+                                                             float *__restrict__ Gp, float *__restrict__ term) {
+    constexpr int QN = (D + kWave - 1) / kWave;
+    const int lane = threadIdx.x & 63;
+    const int w = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (w >= 2 * n) return;
+    const int side = w / n, i = w - side * n;
+    const float *a = views + ((size_t)(2 * side) * n + i) * D, *b = views + ((size_t)(2 * side + 1) * n + i) * D;
+    const float *pa = dA + (size_t)w * D, *pb = dV + (size_t)w * D;
+    float av[QN], bv[QN], ga[QN], gb[QN], ab = 0.f, aga = 0.f, bgb = 0.f;
+#pragma unroll
+    for (int q = 0; q < QN; ++q) {
+        const int k = lane + q * kWave;
+        av[q] = bv[q] = ga[q] = gb[q] = 0.f;
+        if (k < D) { av[q] = a[k]; bv[q] = b[k]; ga[q] = pa[k] - bv[q]; gb[q] = pb[k] - av[q]; }
+        ab = fmaf(av[q], bv[q], ab); aga = fmaf(av[q], ga[q], aga); bgb = fmaf(bv[q], gb[q], bgb);
+    }
+    ab = wave_sum(ab); aga = wave_sum(aga); bgb = wave_sum(bgb);
+    const float n1 = nrm[(size_t)(2 * side) * n + i], n2 = nrm[(size_t)(2 * side + 1) * n + i];
+    float *G = (side ? Gp : Gu) + (size_t)i * D;
+#pragma unroll
+    for (int q = 0; q < QN; ++q) {
+        const int k = lane + q * kWave;
+        if (k < D) {
+            const float d1 = ssl_keep(masks, key, 2 * side, n, i, D, k, p) ? (ga[q] - av[q] * aga) / n1 : 0.f;
+            const float d2 = ssl_keep(masks, key, 2 * side + 1, n, i, D, k, p) ? (gb[q] - bv[q] * bgb) / n2 : 0.f;
+            G[k] += c * d1 + c * d2;
+        }
+    }
+    if (lane == 0) term[(size_t)side * n4 + i] = lse[(size_t)side * n4 + i] - ab * inv_tau;
+}
+
+// loss[side] = (sum_i term[side][i]) / n: one block per side, a strided sum and a fixed tree (deterministic)
+__global__ __launch_bounds__(kBlock) void ssl_loss_kernel(const float *__restrict__ term, int n, int n4, float *__restrict__ loss) {
+    __shared__ float red[kBlock];
+    const float *t = term + (size_t)blockIdx.x * n4;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += kBlock) s += t[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = kBlock / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[blockIdx.x] = red[0] / (float)n;
+}
+
+// ================================================================================================
 // CLeaR spectral-feature-augmentation L1 term (attack/White/CLeaR.py:98-125)
 // ================================================================================================
 // H = rows of X with multiplicities w (H is never materialised: a real user's row appears T times, a target's row U times,
@@ -5112,6 +5211,72 @@ int arl_simgcl_perturb_rng_f32(const float *src, float *dst, int64_t n, int64_t 
     ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
+
+// splits of the streamed view: about 512 workgroups per pass, at least 256 streamed rows per split
+static int ssl_nce_splits(int64_t n) {
+    const int64_t row_blocks = (n + 63) / 64;
+    int64_t s = (512 + row_blocks - 1) / row_blocks;
+    const int64_t max_s = (n + 255) / 256;
+    if (s > max_s) s = max_s;
+    if (s > 64) s = 64;
+    return (int)(s < 1 ? 1 : s);
+}
+
+int64_t arl_ssl_dropout_nce_workspace_bytes(int64_t n, int64_t d) {
+    if (n <= 0 || d <= 0) return 0;
+    const int64_t n4 = (n + 3) & ~3ll, ns = ssl_nce_splits(n);
+    // views [4][n][d], nrm [4][n4], split partials [ns][n][d] + row sums [ns][n4], dA and dV [2][n][d] each, lse and term [2][n4] each
+    return (int64_t)sizeof(float) * (4 * n * d + 4 * n4 + ns * n * d + ns * n4 + 4 * n * d + 4 * n4);
+}
+
+#define ARL_SSL_BY_WIDTH(KERNEL, GRID, ...)                                                                                       \
+    do {                                                                                                                          \
+        if (d == 16) hipLaunchKernelGGL((KERNEL<16>), GRID, dim3(kBlock), 0, st, __VA_ARGS__);                                    \
+        else if (d == 32) hipLaunchKernelGGL((KERNEL<32>), GRID, dim3(kBlock), 0, st, __VA_ARGS__);                               \
+        else if (d == 64) hipLaunchKernelGGL((KERNEL<64>), GRID, dim3(kBlock), 0, st, __VA_ARGS__);                               \
+        else hipLaunchKernelGGL((KERNEL<128>), GRID, dim3(kBlock), 0, st, __VA_ARGS__);                                           \
+        ARL_LAUNCH_CHECK();                                                                                                       \
+    } while (0)
+
+int arl_ssl_dropout_nce_f32(const float *Xu, const float *Xp, int64_t n, int64_t d, float p, float tau, float upstream, uint64_t seed,
+                            uint64_t stream_id, const uint32_t *masks, float *Gu, float *Gp, float *loss, void *workspace, arl_stream_t stream) {
+    if (!Xu || !Xp || !Gu || !Gp || !loss || !workspace) return ARL_E_NULL;
+    if (d != 16 && d != 32 && d != 64 && d != 128) return ARL_E_DIM;
+    if (n <= 0 || n > 0x7fffffffll / 128 || !(p >= 0.f && p < 1.f) || !(tau >= 0.023f)) return ARL_E_ARG;     // tau: the all-rows kernels' fixed shift
+    if (((uintptr_t)Xu | (uintptr_t)Xp | (uintptr_t)Gu | (uintptr_t)Gp | (uintptr_t)workspace) & 15) return ARL_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long key = seed ^ (stream_id * 0x9E3779B97F4A7C15ull);          // the same (seed, stream) hash as arl_simgcl_perturb_rng_f32
+    key += 0x9E3779B97F4A7C15ull; key = (key ^ (key >> 30)) * 0xBF58476D1CE4E5B9ull; key = (key ^ (key >> 27)) * 0x94D049BB133111EBull; key ^= key >> 31;
+    const int ni = (int)n;
+    const int64_t n4 = (n + 3) & ~3ll, nd = n * d;
+    const int ns = ssl_nce_splits(n);
+    const int split_len = (int)((n + ns - 1) / ns);
+    const float s = 1.0f / (1.0f - p), inv_tau = 1.0f / tau;
+    float *views = (float *)workspace, *nrm = views + 4 * nd, *part = nrm + 4 * n4, *sums = part + ns * nd, *dA = sums + ns * n4, *dV = dA + 2 * nd,
+          *lse = dV + 2 * nd, *term = lse + 2 * n4;
+    ARL_SSL_BY_WIDTH(ssl_views_kernel, dim3((unsigned)((4 * n + kWavesPerBlock - 1) / kWavesPerBlock)), Xu, Xp, ni, p, s, key, masks, views, nrm);
+    const dim3 grid((unsigned)((n + 63) / 64), (unsigned)ns);
+    const long long n4v = nd / 4;
+    for (int side = 0; side < 2; ++side) {
+        const float *A = views + (2 * side) * nd, *V = views + (2 * side + 1) * nd;
+        float *lse_s = lse + side * n4, *dA_s = dA + side * nd, *dV_s = dV + side * nd;
+        // lse and dA = sum_j P_ij b_j: view 1 resident, view 2 streamed in splits, unnormalised partials folded in split order
+        ARL_NCE_BY_WIDTH(true, true, true, grid, A, ni, V, ni, split_len, inv_tau, (const float *)nullptr, part, sums);
+        hipLaunchKernelGGL(nce_allrows_fold_norm_kernel, dim3(grid_for(n4v, kBlock)), dim3(kBlock), 0, st, (const float4 *)part, (const float *)sums, ns, ni,
+                           (int)(d / 4), inv_tau, lse_s, (float4 *)dA_s);
+        ARL_LAUNCH_CHECK();
+        // dV = sum_i P_ij a_i: view 2 resident, view 1 streamed in splits with its log-sum-exp, partials folded in split order
+        ARL_NCE_BY_WIDTH(true, false, false, grid, V, ni, A, ni, split_len, inv_tau, (const float *)lse_s, part, (float *)nullptr);
+        hipLaunchKernelGGL(nce_allrows_fold_kernel, dim3(grid_for(n4v, kBlock)), dim3(kBlock), 0, st, (const float4 *)part, ns, n4v, (float4 *)dV_s);
+        ARL_LAUNCH_CHECK();
+    }
+    ARL_SSL_BY_WIDTH(ssl_finish_kernel, dim3((unsigned)((2 * n + kWavesPerBlock - 1) / kWavesPerBlock)), views, nrm, dA, dV, lse, ni, (int)n4, p, inv_tau,
+                     upstream * s / ((float)n * tau), key, masks, Gu, Gp, term);
+    hipLaunchKernelGGL(ssl_loss_kernel, dim3(2), dim3(kBlock), 0, st, term, ni, (int)n4, loss);
+    ARL_LAUNCH_CHECK();
+    return ARL_OK;
+}
+#undef ARL_SSL_BY_WIDTH
 
 int arl_simgcl_perturb_f32(float *E, const float *noise, int64_t n, int64_t d, float eps, arl_stream_t stream) {
     if (!E || !noise) return ARL_E_NULL;

@@ -220,9 +220,13 @@ class PropagationEngine:
           * G is kept all-zero between steps (batch rows are cleared afterwards) instead of memset per step.
         Same numbers as `step_dense` (which evaluates all 2L hops on the full graph), 2 of the 2L full hops cheaper.
         `rows` = cat(u, U+p, U+n) may be passed in when the caller has it precomputed."""
-        L, A = self.L, self.A
-        if self.optimizer != 'adam' or L == 0 or self.skip0 or L > 8:
+        if self.optimizer != 'adam' or self.L == 0 or self.skip0 or self.L > 8:
             return self.step_dense(u, p, n)
+        return self._step_sparse(u, p, n, rows, None)
+
+    def _step_sparse(self, u, p, n, rows, extra_grad):
+        """step()'s sparse-batch form; extra_grad(): adds a further loss's gradient into the compact rows Gc after the BPR kernel (SSL4Rec)."""
+        L, A = self.L, self.A
         B = u.numel()
         if rows is None:
             rows = torch.cat([u, p + self.U, n + self.U])
@@ -240,6 +244,8 @@ class PropagationEngine:
         # loss + compact per-sample gradients (rows [0,B) users, [B,2B) positives, [2B,3B) negatives of out_c)
         self.Gc.zero_()
         ops.bpr_l2_fwd_bwd(self.out_c, B, self.ar, self.ar, self.arB, self.reg, self.Gc, workspace=self._ws, loss_out=self.loss_out, check_range=False, distinct_rows=True)
+        if extra_grad is not None:
+            extra_grad()
         ops.batch_rows_set_(self.G, self.flags, self.bits, rows, self.Gc, 1.0, check_range=False, dup_bits=self.dup_bits)      # duplicates accumulate in order; rows marked
         # backward (Horner): first hop gathers flagged rows only; G is read through the flags everywhere
         self.t += 1
@@ -253,6 +259,36 @@ class PropagationEngine:
             ops.spmm_adam(A, acc, s, s, self.G, self.E0, self.m, self.v, self.lr, self.t, self.betas, self.eps, zflags=self.flags)
         ops.batch_rows_clear_(self.G, self.flags, self.bits, rows, check_range=False, dup_bits=self.dup_bits)
         return self.loss_out
+
+    def step_ssl4rec(self, u, p, n, cl_rate=1.0, tau=0.2, drop=0.2, masks=None, seed=None, stream_id=None):
+        """One SSL4Rec training iteration (recommender/SSL4Rec.py:58-75, 213-247): the step() schedule (LightGCN mean over layers 0..L, BPR + L2,
+        Adam fused into the last backward hop) plus ONE call of the dropout-view InfoNCE kernel, which adds cl_rate * its gradient into the
+        compact gradient rows [0, B) (users) and [B, 2B) (positives) before they enter G -- the contrastive term reads the same propagated
+        batch rows as the BPR loss, so it costs no extra hop.  masks: optional bool [2 sides][2 views][B][d] (parity tests); default: drawn
+        inside the kernel from a seed taken once from torch's global generator and a running stream number (one per step), or from the
+        caller's (seed, stream_id).  Returns (loss_out, cl_loss) device tensors (no host sync)."""
+        L, A = self.L, self.A
+        if self.optimizer != 'adam' or self.skip0 or L < 1 or L > 8:
+            raise ValueError('step_ssl4rec needs a LightGCN-mean engine (no skip_layer0, 1 <= L <= 8) with Adam')
+        B = u.numel()
+        if self.d not in ops.SSL_NCE_WIDTHS:
+            raise ValueError('step_ssl4rec: embedding size %d unsupported (d in %s)' % (self.d, ops.SSL_NCE_WIDTHS))
+        if masks is not None and tuple(masks.shape) != (2, 2, B, self.d):
+            raise ValueError('step_ssl4rec: masks [2, 2, B, d]')
+        if seed is None:
+            if getattr(self, '_mask_seed', None) is None:
+                self._mask_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                self._mask_stream = 0
+            seed, stream_id = self._mask_seed, self._mask_stream
+            self._mask_stream += 1
+        cl = []
+        def contrastive():
+            loss, _ = ops.ssl_dropout_nce(self.out_c[:B], self.out_c[B:2 * B], drop, tau, G=(self.Gc[:B], self.Gc[B:2 * B]), upstream=cl_rate,
+                                          seed=seed, stream_id=stream_id, masks=masks)
+            cl.append(loss)
+        self._step_sparse(u, p, n, None, contrastive)
+        cl = cl[0]
+        return self.loss_out, cl_rate * (cl[1] + cl[0])
 
     # ---- NGCF (recommender/NGCF.py:47-64,197-212): the whole training iteration without autograd or a torch optimizer.  Per layer ONE hop
     # P = A E (A(E W1) = (A E) W1) and the fp32-MFMA dense part (ops.ngcf_dense_*); sparse-batch schedule as in step(): the LAST layer is

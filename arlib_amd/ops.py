@@ -993,6 +993,57 @@ def nce_allrows(A, V, tau, want_grad=True, want_dV=True, lse=None):
     return lse, dA, dV
 
 
+SSL_NCE_WIDTHS = NCE_ALLROWS_WIDTHS
+
+
+def pack_view_masks(masks):
+    """Bool / 0-1 masks [2 sides][2 views][n][d] -> the packed int32 words arl_ssl_dropout_nce_f32 reads (bit b = (sv * n + i) * d + k of word b >> 5)."""
+    bits = masks.reshape(-1).to(torch.int64)
+    pad = (-bits.numel()) % 32
+    if pad:
+        bits = torch.cat([bits, bits.new_zeros(pad)])
+    words = (bits.view(-1, 32) << torch.arange(32, device=bits.device, dtype=torch.int64)).sum(1)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).contiguous()
+
+
+def ssl_dropout_nce(Xu, Xp, p, tau, G=None, upstream=1.0, seed=0, stream_id=0, masks=None):
+    """SSL4Rec's contrastive term (recommender/SSL4Rec.py:232-247): two dropout(p) views of the user rows Xu [n, d] and of the positive rows
+    Xp [n, d] (duplicates kept) and InfoNCE(view1, view2, tau) per side, forward and backward in one call.  Returns loss [2] (users,
+    positives; un-scaled) and G = (Gu, Gp): G[side][i] += upstream * dL_side/dX[i].  G: None (zeros are allocated) or a pair of [n, d]
+    tensors accumulated in place.  masks: None = drawn inside the kernel from (seed, stream_id) (rule in include/arlib_amd.h), or
+    bool [2 sides][2 views][n][d] (keep = True), or its packed int32 words (pack_view_masks)."""
+    _dev(Xu, torch.float32, 'Xu', 2); _dev(Xp, torch.float32, 'Xp', 2)
+    if Xu.shape != Xp.shape:
+        raise ValueError('ssl_dropout_nce: Xu, Xp [n, d] of the same shape')
+    n, d = Xu.shape
+    if d not in SSL_NCE_WIDTHS:
+        raise ValueError('ssl_dropout_nce: embedding size %d unsupported (d in %s)' % (d, SSL_NCE_WIDTHS))
+    if n == 0:
+        raise ValueError('ssl_dropout_nce: empty batch')
+    if not 0.0 <= float(p) < 1.0 or not float(tau) >= NCE_ALLROWS_MIN_TAU:
+        raise ValueError('ssl_dropout_nce: need 0 <= p < 1 and tau >= %g' % NCE_ALLROWS_MIN_TAU)
+    if G is None:
+        G = (torch.zeros_like(Xu), torch.zeros_like(Xp))
+    Gu, Gp = G
+    _dev(Gu, torch.float32, 'Gu', 2); _dev(Gp, torch.float32, 'Gp', 2)
+    if Gu.shape != Xu.shape or Gp.shape != Xu.shape:
+        raise ValueError('ssl_dropout_nce: Gu, Gp [n, d]')
+    if masks is not None:
+        if masks.dtype != torch.int32:
+            if tuple(masks.shape) != (2, 2, n, d):
+                raise ValueError('ssl_dropout_nce: masks [2, 2, n, d]')
+            masks = pack_view_masks(masks)
+        _dev(masks, torch.int32, 'masks', 1)
+        if masks.numel() != (4 * n * d + 31) // 32 or masks.device != Xu.device:
+            raise ValueError('ssl_dropout_nce: packed masks need %d words on the device of Xu' % ((4 * n * d + 31) // 32))
+    L = _lib.lib()
+    ws = torch.empty(L.arl_ssl_dropout_nce_workspace_bytes(n, d) // 4, dtype=torch.float32, device=Xu.device)
+    loss = torch.empty(2, dtype=torch.float32, device=Xu.device)
+    check(L.arl_ssl_dropout_nce_f32(_ptr(Xu), _ptr(Xp), n, d, float(p), float(tau), float(upstream), int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 64 - 1),
+                                    _ptr(masks), _ptr(Gu), _ptr(Gp), _ptr(loss), _ptr(ws), _stream()), 'arl_ssl_dropout_nce_f32')
+    return loss, (Gu, Gp)
+
+
 def normalize_rows(X):
     """(Y, nrm) = (F.normalize(X, dim=1), max(||X_r||, 1e-12)) in one pass (recommender/NCL.py:98-99)."""
     _dev(X, torch.float32, 'X', 2)

@@ -419,6 +419,10 @@ class Recommender:
     def _on_epoch_end(self, model, epoch, maxEpoch, gradIterationNum):
         pass
 
+    def _print_step(self, epoch, n, lo=None, batch_loss=None):
+        """The loop's line every print_every batches: lo = the fused step's loss vector, batch_loss = the autograd route's loss tensor."""
+        print('training:', epoch + 1, 'batch', n, 'batch_loss:', float(lo[0] + lo[1]) if lo is not None else batch_loss.item())
+
     def _train_loop(self, Epoch, optimizer, evalNum, requires_embgrad=False, requires_adjgrad=False, gradIterationNum=10, force_autograd=False):
         self.bestPerformance = []
         model = self.model.cuda()
@@ -485,7 +489,7 @@ class Recommender:
                 if eng is not None:
                     lo = self._fused_step(eng, u, p, ng)
                     if n % self.print_every == 0:
-                        print('training:', epoch + 1, 'batch', n, 'batch_loss:', float(lo[0] + lo[1]))
+                        self._print_step(epoch, n, lo=lo)
                     continue
                 model.train()
                 ul, pl, nl = u.long(), p.long(), ng.long()
@@ -521,7 +525,7 @@ class Recommender:
                 self._after_backward(model, epoch, maxEpoch, gradIterationNum)
                 optimizer.step()
                 if n % self.print_every == 0:
-                    print('training:', epoch + 1, 'batch', n, 'batch_loss:', batch_loss.item())
+                    self._print_step(epoch, n, batch_loss=batch_loss)
             if torch.cuda.is_available():
                 torch.cuda.synchronize()
             # wall clock of the epoch's batch loop alone (sampler draw, evaluation and the epoch-end forward excluded)

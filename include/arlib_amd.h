@@ -512,6 +512,26 @@ int arl_nce_allrows_lse_f32(const float *A, int64_t nA, const float *V, int64_t 
 int arl_nce_allrows_grad_f32(const float *A, int64_t nA, const float *V, int64_t nV, int64_t d, float tau, float *lse, int32_t lse_given,
                              float *dA, float *dV, void *workspace, arl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * SSL4Rec's contrastive term, forward and backward in one call -- replaces recommender/SSL4Rec.py:232-247 (item_encoding: two
+ * nn.Dropout(p) views of the batch's propagated user rows and of its positive-item rows; cal_cl_loss: InfoNCE of each pair) and the
+ * autograd of util/loss.py:42-49.  Xu, Xp [n, d]: the compact rows of the two sides (duplicate positions kept, never merged).  Per side:
+ *   V1 = X * M1 * s, V2 = X * M2 * s, s = 1 / (1 - p);  a = V1 / max(||V1||, 1e-12), b = V2 / max(||V2||, 1e-12)   (row-wise)
+ *   loss[side] = mean_i( log sum_j exp(<a_i, b_j> / tau) - <a_i, b_i> / tau )          (loss[0]: users, loss[1]: positives)
+ *   G[i] += upstream * s * (M1 * dL/dV1 + M2 * dL/dV2)                                   (Gu for the users, Gp for the positives; per position)
+ * Mask bit of (side, view, position i, column k) with sv = 2 * side + view:
+ *   masks != NULL: bit b = (sv * n + i) * d + k of the packed words, (masks[b >> 5] >> (b & 31)) & 1   ([2 sides][2 views][n][d] bits);
+ *   masks == NULL: kept iff (splitmix64(key ^ (((sv << 32) + i) * d + k)) >> 40) * 2^-24 >= p, where key is the hash of (seed, stream_id)
+ *                  that arl_simgcl_perturb_rng_f32 forms:  key = splitmix64(seed ^ (stream_id * 0x9E3779B97F4A7C15)).
+ * The n x n logits are never stored: the products run on the all-rows InfoNCE kernels (exact fp32 MFMA, fixed log-sum-exp shift, hence
+ * tau >= 0.023), the streamed view split so that B = 2048 fills the chip, partials folded in a fixed order; no float atomics, so two
+ * calls give bit-identical outputs.  d in {16, 32, 64, 128} (else ARL_E_DIM); 0 <= p < 1, n <= 2^31 / 128 and 16-byte aligned
+ * Xu, Xp, Gu, Gp, workspace (else ARL_E_ARG).  workspace: arl_ssl_dropout_nce_workspace_bytes(n, d) bytes.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t arl_ssl_dropout_nce_workspace_bytes(int64_t n, int64_t d);
+int arl_ssl_dropout_nce_f32(const float *Xu, const float *Xp, int64_t n, int64_t d, float p, float tau, float upstream, uint64_t seed,
+                            uint64_t stream_id, const uint32_t *masks, float *Gu, float *Gp, float *loss, void *workspace, arl_stream_t stream);
+
 /* F.normalize(x, dim=1) of a whole table and its autograd in one pass each (the normalisations around the all-rows InfoNCE,
  * recommender/NCL.py:98-99, 110-111; d % 4 == 0, d <= 256, 16-byte aligned tables):
  *   Y = X / max(||X_r||, 1e-12), nrm[r] = max(||X_r||, 1e-12);   dX = scale * (dY - Y <Y, dY>) / nrm  (dX may alias dY;
