@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ARLIB_AMD_LIB') or os.path.join(_HERE, 'lib', 'libarlib_amd.so')      # override: developer builds (e.g. `make prof`)
-ABI_VERSION = 26
+ABI_VERSION = 27
 _lib = None
 
 
@@ -118,6 +118,17 @@ _SIGS = {
     'arl_nce_allrows_grad_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _f, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
     'arl_ssl_dropout_nce_workspace_bytes': (_i64, [_i64, _i64]),
     'arl_ssl_dropout_nce_f32': (C.c_int, [_vp, _vp, _i64, _i64, _f, _f, _f, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'arl_gan_gemm_f32': (C.c_int, [_i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
+    'arl_gan_spmm_f32': (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    'arl_gan_transpose_f32': (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    'arl_gan_rows_f32': (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'arl_gan_dz2_f32': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    'arl_gan_colsum_workspace_bytes': (_i64, [_i64, _i64]),
+    'arl_gan_colsum_f32': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    'arl_gan_hash_key': (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    'arl_gan_template_i32': (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    'arl_gan_hash_mask_u8': (C.c_int, [_i64, _i64, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
+    'arl_gan_threshold_f32': (C.c_int, [_vp, _i64, _i64, _f, _vp, _vp, _vp, _vp]),
     'arl_comm_load': (C.c_int, [C.c_char_p]),
     'arl_comm_unique_id': (C.c_int, [_vp]),
     'arl_comm_init': (C.c_int, [_vp, _i64, _i64, _i64, C.POINTER(C.c_void_p)]),

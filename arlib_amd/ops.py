@@ -1828,3 +1828,227 @@ def spmm_tiled_adam(P, X, alpha, beta, Z, Pm, M, V, lr, step, betas=(0.9, 0.999)
                                                lr, betas[0], betas[1], eps, int(step), _stream()), 'arl_spmm_csr_adam_f32 (hub rows)')
     if tok is not None:
         EVENT_HOOK.end(tok)
+
+
+# ================================================================================================ AUSH's GAN (arl_gan_*, csrc/arl_gan.hip)
+GAN_MAX_ELEMS = 2 ** 31 - 1          # every F x S and S x S operand of the kernels is indexed within this many elements
+GAN_EPI_STORE, GAN_EPI_BIAS_SIGMOID, GAN_EPI_RELU_MASK = 0, 1, 2
+
+
+def gan_supported(F, S):
+    """True when the fused GAN kernels take an F x S template (else the attack composes torch ops: attack/Gray/_gan.py)."""
+    F, S = int(F), int(S)
+    return F >= 1 and S >= 1 and F * S <= GAN_MAX_ELEMS and S * S <= GAN_MAX_ELEMS
+
+
+def _gan_size(F, S, what):
+    if not gan_supported(F, S):
+        raise ValueError('%s: F = %d, S = %d outside the kernels\' limits (F, S >= 1, F * S and S * S <= 2^31 - 1)' % (what, F, S))
+
+
+def gan_template_supported(F, S):
+    """True when the template kernels (gan_template, gan_hash_mask) take an F x S template: they index F x S only."""
+    F, S = int(F), int(S)
+    return F >= 0 and S >= 1 and F * S <= GAN_MAX_ELEMS
+
+
+def _gan_template_size(F, S, what):
+    if not gan_template_supported(F, S):
+        raise ValueError('%s: F = %d, S = %d outside the template kernel\'s limits (S >= 1, F * S <= 2^31 - 1)' % (what, F, S))
+
+
+def gan_gemm(A, B, trans_a=False, trans_b=False, epilogue=GAN_EPI_STORE, bias=None, aux=None):
+    """C = op(A) op(B) on the exact-fp32 matrix cores, op = transpose when asked; epilogue: GAN_EPI_STORE, GAN_EPI_BIAS_SIGMOID
+    (sigmoid(C + bias)) or GAN_EPI_RELU_MASK (C where aux > 0, else 0)."""
+    _dev(A, torch.float32, 'A', 2); _dev(B, torch.float32, 'B', 2)
+    M, K = (A.shape[1], A.shape[0]) if trans_a else tuple(A.shape)
+    K2, N = (B.shape[1], B.shape[0]) if trans_b else tuple(B.shape)
+    if K != K2:
+        raise ValueError('gan_gemm: inner sizes %d and %d differ' % (K, K2))
+    if max(M * N, M * K, K * N) > GAN_MAX_ELEMS:
+        raise ValueError('gan_gemm: operands past 2^31 - 1 elements')
+    sam, sak = (1, A.shape[1]) if trans_a else (A.shape[1], 1)
+    sbk, sbn = (1, B.shape[1]) if trans_b else (B.shape[1], 1)
+    if epilogue == GAN_EPI_BIAS_SIGMOID:
+        _dev(bias, torch.float32, 'bias', 1)
+        if bias.numel() != N:
+            raise ValueError('gan_gemm: bias [N]')
+    elif epilogue == GAN_EPI_RELU_MASK:
+        _dev(aux, torch.float32, 'aux', 2)
+        if tuple(aux.shape) != (M, N):
+            raise ValueError('gan_gemm: aux [M, N]')
+    elif epilogue != GAN_EPI_STORE:
+        raise ValueError('gan_gemm: unknown epilogue %r' % (epilogue,))
+    Cm = torch.empty(M, N, dtype=torch.float32, device=A.device)
+    check(_lib.lib().arl_gan_gemm_f32(M, N, K, _ptr(A), sam, sak, _ptr(B), sbk, sbn, _ptr(Cm), int(epilogue), _ptr(bias), _ptr(aux), _stream()),
+          'arl_gan_gemm_f32')
+    return Cm
+
+
+def _gan_csr(rowptr, col, val, n_rows, n_cols, what):
+    _dev(rowptr, torch.int64, what + ' rowptr', 1); _dev(col, torch.int32, what + ' col', 1); _dev(val, torch.float32, what + ' val', 1)
+    if rowptr.numel() != n_rows + 1 or col.numel() != val.numel():
+        raise ValueError('%s: rowptr [n_rows + 1], col and val of one length' % what)
+    nnz = col.numel()
+    if nnz:
+        if int(rowptr[0]) != 0 or int(rowptr[-1]) != nnz or bool((rowptr[1:] < rowptr[:-1]).any()):
+            raise ValueError('%s: rowptr must rise from 0 to nnz' % what)
+        if int(col.min()) < 0 or int(col.max()) >= n_cols:
+            raise IndexError('%s: column index out of range' % what)
+    elif int(rowptr.abs().max()) != 0:
+        raise ValueError('%s: rowptr of an empty matrix must be 0' % what)
+
+
+def gan_spmm(rowptr, col, val, X, bias=None, relu=False, check_range=True):
+    """out [n_rows, N] = sparse (rowptr, col, val) x X [*, N] (+ bias, then relu if asked), entries in CSR order."""
+    _dev(X, torch.float32, 'X', 2)
+    n_rows, N = rowptr.numel() - 1, X.shape[1]
+    if check_range:
+        _gan_csr(rowptr, col, val, n_rows, X.shape[0], 'gan_spmm')
+    if bias is not None:
+        _dev(bias, torch.float32, 'bias', 1)
+        if bias.numel() != N:
+            raise ValueError('gan_spmm: bias [N]')
+    out = torch.empty(n_rows, N, dtype=torch.float32, device=X.device)
+    check(_lib.lib().arl_gan_spmm_f32(n_rows, N, _ptr(rowptr), _ptr(col), _ptr(val), _ptr(X), _ptr(bias), int(bool(relu)), _ptr(out), _stream()),
+          'arl_gan_spmm_f32')
+    return out
+
+
+def gan_transpose(A):
+    _dev(A, torch.float32, 'A', 2)
+    At = torch.empty(A.shape[1], A.shape[0], dtype=torch.float32, device=A.device)
+    check(_lib.lib().arl_gan_transpose_f32(_ptr(A), A.shape[0], A.shape[1], _ptr(At), _stream()), 'arl_gan_transpose_f32')
+    return At
+
+
+def gan_rows(Y, Td, n_targets, wD, bD):
+    """Per-row partials rows [F, 4] = (Y.w_D, Td.w_D, sum (Y - Td)^2, target shill sum), losses [3] = (loss1, loss2, dloss1/db_D),
+    coef [2 F] (dloss1/dlogits of the real and the fake rows) and pf [F] = D(Y)."""
+    _dev(Y, torch.float32, 'Y', 2); _dev(Td, torch.float32, 'Td', 2); _dev(wD, torch.float32, 'wD')
+    F, S = Y.shape
+    _gan_size(F, S, 'gan_rows')
+    if Td.shape != Y.shape or wD.numel() != S or bD.numel() != 1 or not 0 <= int(n_targets) <= S:
+        raise ValueError('gan_rows: Y, Td [F, S], wD [S], bD [1], 0 <= T <= S')
+    _dev(bD, torch.float32, 'bD')
+    rows = torch.empty(F, 4, dtype=torch.float32, device=Y.device)
+    losses = torch.empty(3, dtype=torch.float32, device=Y.device)
+    coef = torch.empty(2 * F, dtype=torch.float32, device=Y.device)
+    pf = torch.empty(F, dtype=torch.float32, device=Y.device)
+    check(_lib.lib().arl_gan_rows_f32(_ptr(Y), _ptr(Td), F, S, int(n_targets), _ptr(wD), _ptr(bD), _ptr(rows), _ptr(losses), _ptr(coef), _ptr(pf),
+                                      _stream()), 'arl_gan_rows_f32')
+    return rows, losses, coef, pf
+
+
+def gan_dz2(Y, Td, rows, pf, wD, n_targets):
+    _dev(Y, torch.float32, 'Y', 2); _dev(Td, torch.float32, 'Td', 2); _dev(rows, torch.float32, 'rows', 2); _dev(pf, torch.float32, 'pf', 1)
+    _dev(wD, torch.float32, 'wD')
+    F, S = Y.shape
+    _gan_size(F, S, 'gan_dz2')
+    if Td.shape != Y.shape or tuple(rows.shape) != (F, 4) or pf.numel() != F or wD.numel() != S or not 0 <= int(n_targets) <= S:
+        raise ValueError('gan_dz2: Y, Td [F, S], rows [F, 4], pf [F], wD [S], 0 <= T <= S')
+    dZ2 = torch.empty_like(Y)
+    check(_lib.lib().arl_gan_dz2_f32(_ptr(Y), _ptr(Td), _ptr(rows), _ptr(pf), _ptr(wD), F, S, int(n_targets), _ptr(dZ2), _stream()), 'arl_gan_dz2_f32')
+    return dZ2
+
+
+def gan_colsum(A, wa=None, Bm=None, wb=None):
+    """out [S] = sum_r wa[r] A[r] + wb[r] Bm[r] (wa None = 1, Bm None = no second term), folded in a fixed order."""
+    _dev(A, torch.float32, 'A', 2)
+    F, S = A.shape
+    _gan_size(F, S, 'gan_colsum')
+    if wa is not None:
+        _dev(wa, torch.float32, 'wa')
+        if wa.numel() != F:
+            raise ValueError('gan_colsum: wa [F]')
+    if Bm is not None:
+        _dev(Bm, torch.float32, 'Bm', 2); _dev(wb, torch.float32, 'wb')
+        if Bm.shape != A.shape or wb.numel() != F:
+            raise ValueError('gan_colsum: Bm [F, S], wb [F]')
+    L = _lib.lib()
+    ws = torch.empty(L.arl_gan_colsum_workspace_bytes(F, S) // 4, dtype=torch.float32, device=A.device)
+    out = torch.empty(S, dtype=torch.float32, device=A.device)
+    check(L.arl_gan_colsum_f32(_ptr(A), _ptr(wa), _ptr(Bm), _ptr(wb), F, S, _ptr(out), _ptr(ws), _stream()), 'arl_gan_colsum_f32')
+    return out
+
+
+def gan_template(user_set, ui_rowptr, ui_col, ui_val, pos, items, mask=None, item_p=None, seed=0, call=0):
+    """One step's F x S template as CSR (rowptr int64, col int32, val float32) from the interaction CSR (U x I, ascending columns per row),
+    pos [I] (selectItem position or -1) and items [S] (selectItem); mask: uint8 [F, S] (injected) or None = the counter hash of
+    (seed, call) against item_p [I] (include/arlib_amd.h, arl_gan_template_i32)."""
+    _dev(user_set, torch.int32, 'user_set', 1); _dev(pos, torch.int32, 'pos', 1); _dev(items, torch.int32, 'items', 1)
+    F, S, U, I = user_set.numel(), items.numel(), ui_rowptr.numel() - 1, pos.numel()
+    _gan_template_size(F, S, 'gan_template')
+    _gan_csr(ui_rowptr, ui_col, ui_val, U, I, 'gan_template interactions')
+    if F > U or S > I:
+        raise ValueError('gan_template: F <= U and S <= I needed (row r and position j are read as a user and an item)')
+    if F and (int(user_set.min()) < 0 or int(user_set.max()) >= U):
+        raise IndexError('gan_template: user id out of range')
+    if int(pos.min()) < -1 or int(pos.max()) >= S or int(items.min()) < 0 or int(items.max()) >= I:
+        raise IndexError('gan_template: pos / items out of range')
+    if mask is not None:
+        _dev(mask, torch.uint8, 'mask', 2)
+        if tuple(mask.shape) != (F, S):
+            raise ValueError('gan_template: mask [F, S]')
+    else:
+        _dev(item_p, torch.float32, 'item_p', 1)
+        if item_p.numel() != I:
+            raise ValueError('gan_template: item_p [I]')
+    dev = user_set.device
+    L = _lib.lib()
+    seed, call = int(seed) & (2 ** 64 - 1), int(call) & (2 ** 64 - 1)
+    counts = torch.zeros(F, dtype=torch.int64, device=dev)
+    args = lambda optr, cnt, oc, ov: (F, S, U, _ptr(user_set), _ptr(ui_rowptr), _ptr(ui_col), _ptr(ui_val), _ptr(pos), _ptr(items), _ptr(mask),
+                                     _ptr(item_p), seed, call, optr, cnt, oc, ov, _stream())
+    check(L.arl_gan_template_i32(*args(None, _ptr(counts), None, None)), 'arl_gan_template_i32 (count)')
+    rowptr = torch.zeros(F + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=rowptr[1:])
+    nnz = int(rowptr[-1])
+    col = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+    val = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
+    check(L.arl_gan_template_i32(*args(_ptr(rowptr), None, _ptr(col), _ptr(val))), 'arl_gan_template_i32 (fill)')
+    return rowptr, col[:nnz], val[:nnz]
+
+
+def gan_hash_keep(rows, items_of_cols, item_p, seed, call):
+    """Host restatement of the template kernel's counter hash (include/arlib_amd.h, arl_gan_template_i32): True where the mask of (row, item)
+    is set -- (splitmix64(key ^ (row * 2^32 + item)) >> 40) * 2^-24 < item_p[item] in float32, key = arl_gan_hash_key(seed, call).  The
+    template past the kernel's limits uses it, so that both routes see the same masks."""
+    key = np.uint64(_lib.lib().arl_gan_hash_key(int(seed) & (2 ** 64 - 1), int(call) & (2 ** 64 - 1)))
+    x = (np.asarray(rows, np.uint64) << np.uint64(32)) + np.asarray(items_of_cols, np.uint64)
+    with np.errstate(over='ignore'):
+        x = (key ^ x) + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        x = x ^ (x >> np.uint64(31))
+    u = (x >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    return u < np.asarray(item_p, np.float32)[np.asarray(items_of_cols, np.int64)]
+
+
+def gan_hash_mask(F, items, item_p, seed=0, call=0):
+    """The counter-hash masks [F, S] (uint8) that gan_template draws when no mask is injected."""
+    _dev(items, torch.int32, 'items', 1); _dev(item_p, torch.float32, 'item_p', 1)
+    S = items.numel()
+    _gan_template_size(F, S, 'gan_hash_mask')
+    if S and (int(items.min()) < 0 or int(items.max()) >= item_p.numel()):
+        raise IndexError('gan_hash_mask: items out of range')
+    out = torch.empty(int(F), S, dtype=torch.uint8, device=items.device)
+    check(_lib.lib().arl_gan_hash_mask_u8(int(F), S, _ptr(items), _ptr(item_p), int(seed) & (2 ** 64 - 1), int(call) & (2 ** 64 - 1), _ptr(out), _stream()),
+          'arl_gan_hash_mask_u8')
+    return out
+
+
+def gan_threshold(Y, thr=0.1):
+    """CSR (rowptr int64, col int32) of Y > thr, columns ascending per row."""
+    _dev(Y, torch.float32, 'Y', 2)
+    F, S = Y.shape
+    _gan_size(max(F, 1), S, 'gan_threshold')
+    L = _lib.lib()
+    counts = torch.zeros(F, dtype=torch.int64, device=Y.device)
+    check(L.arl_gan_threshold_f32(_ptr(Y), F, S, float(thr), None, _ptr(counts), None, _stream()), 'arl_gan_threshold_f32 (count)')
+    rowptr = torch.zeros(F + 1, dtype=torch.int64, device=Y.device)
+    torch.cumsum(counts, 0, out=rowptr[1:])
+    nnz = int(rowptr[-1])
+    col = torch.empty(max(nnz, 1), dtype=torch.int32, device=Y.device)
+    check(L.arl_gan_threshold_f32(_ptr(Y), F, S, float(thr), _ptr(rowptr), None, _ptr(col), _stream()), 'arl_gan_threshold_f32 (fill)')
+    return rowptr, col[:nnz]

@@ -541,6 +541,52 @@ int arl_normalize_rows_bwd_f32(const float *Y, const float *nrm, const float *dY
                                float *dX, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * AUSH's GAN (attack/Gray/AUSH.py; arlib_amd/csrc/arl_gan.hip).  G: Y = sigmoid(relu(T W1^T + b1) W2^T + b2) over an F x S template T,
+ * D(x) = sigmoid(x w_D + b_D).  Every operand with F x S or S x S elements must stay within 2^31 - 1 elements (else ARL_E_RANGE).
+ *
+ * arl_gan_gemm_f32: C [M, N] (row-major, ld N) = sum_k A(m, k) B(k, n), A(m, k) = A[m * sam + k * sak], B(k, n) = B[k * sbk + n * sbn];
+ *   sak or sam must be 1, sbn or sbk must be 1 (else ARL_E_ARG).  epilogue 0: C = acc; 1: C = sigmoid(acc + bias[n]); 2: C = aux[m, n] > 0 ?
+ *   acc : 0 (aux [M, N]).  Exact fp32 products on v_mfma_f32_16x16x4_f32, the whole K range per output tile in ascending order: deterministic.
+ * arl_gan_spmm_f32: out [n_rows, N] = (bias ? bias[n] : 0) + sum_{k in row r} val[k] X[col[k], :] (X row-major [*, N]), then relu if asked;
+ *   entries summed in CSR order (int64 rowptr, int32 col).
+ * arl_gan_transpose_f32: At [Cn, R] = A [R, Cn]^T (A != At).
+ * arl_gan_rows_f32: per row of Y and the dense template Td ([F, S]): rows [F, 4] = (Y_r.w_D, Td_r.w_D, sum (Y - Td)^2, sum over the last T
+ *   columns of (1 - Y)); then, in one fixed-order workgroup, losses [3] = (loss1 = -(mean log D(Td) + mean log(1 - D(Y))),
+ *   loss2 = mean log D(Td) + mean log(1 - D(Y)) + mean_r s_r^2 + mean (Y - Td)^2, dloss1/db_D), coef [2 F] = (-(1 - D(Td_r)) / F,
+ *   D(Y_r) / F) and pf [F] = D(Y_r).  b_D is a device scalar.
+ * arl_gan_dz2_f32: dZ2 = dloss2/dY * Y (1 - Y) with dloss2/dY = 2 (Y - Td) / (F S) - (2 s_r / F) [c >= S - T] - (pf_r / F) w_D[c].
+ * arl_gan_colsum_f32: out [S] = sum_r (wa ? wa[r] : 1) A[r, :] + (Bm ? wb[r] Bm[r, :] : 0) over F rows, in chunks of 64 rows folded in
+ *   ascending order; workspace: arl_gan_colsum_workspace_bytes(F, S) bytes.
+ * arl_gan_template_i32: the template of one step.  Row r takes the entries of interaction row user_set[r] (CSR with ascending columns)
+ *   whose item c has pos[c] >= 0, in that row's order: column j = pos[c], value = interact[r, j] * mask(r, j) (row r and position j read as
+ *   a user and an item id, as the reference does; explicit zeros kept).  mask(r, j) = mask[r * S + j] when mask != NULL, else
+ *   1 iff (splitmix64(key ^ (r * 2^32 + items[j])) >> 40) * 2^-24 < item_p[items[j]] with key = arl_gan_hash_key(seed, call).
+ *   Count pass (out_ptr NULL): counts[F].  Fill pass: out_ptr [F + 1] row offsets, writes out_col / out_val.
+ * arl_gan_hash_mask_u8: out [F, S] = mask(r, j) of the counter hash above.
+ * arl_gan_threshold_f32: count pass (out_ptr NULL): counts[r] = #{c : Y[r, c] > thr}; fill pass: ascending columns per row into out_col.
+ * ---------------------------------------------------------------------------------------------- */
+int arl_gan_gemm_f32(int64_t M, int64_t N, int64_t K, const float *A, int64_t sam, int64_t sak, const float *B, int64_t sbk, int64_t sbn, float *C,
+                     int32_t epilogue, const float *bias, const float *aux, arl_stream_t stream);
+int arl_gan_spmm_f32(int64_t n_rows, int64_t N, const int64_t *rowptr, const int32_t *col, const float *val, const float *X, const float *bias,
+                     int32_t relu, float *out, arl_stream_t stream);
+int arl_gan_transpose_f32(const float *A, int64_t R, int64_t Cn, float *At, arl_stream_t stream);
+int arl_gan_rows_f32(const float *Y, const float *Td, int64_t F, int64_t S, int64_t T, const float *wD, const float *bD, float *rows, float *losses,
+                     float *coef, float *pf, arl_stream_t stream);
+int arl_gan_dz2_f32(const float *Y, const float *Td, const float *rows, const float *pf, const float *wD, int64_t F, int64_t S, int64_t T, float *dZ2,
+                    arl_stream_t stream);
+int64_t arl_gan_colsum_workspace_bytes(int64_t F, int64_t S);
+int arl_gan_colsum_f32(const float *A, const float *wa, const float *Bm, const float *wb, int64_t F, int64_t S, float *out, void *workspace,
+                       arl_stream_t stream);
+uint64_t arl_gan_hash_key(uint64_t seed, uint64_t call);
+int arl_gan_template_i32(int64_t F, int64_t S, int64_t n_users, const int32_t *user_set, const int64_t *rowptr, const int32_t *col, const float *val,
+                         const int32_t *pos, const int32_t *items, const uint8_t *mask, const float *item_p, uint64_t seed, uint64_t call,
+                         const int64_t *out_ptr, int64_t *counts, int32_t *out_col, float *out_val, arl_stream_t stream);
+int arl_gan_hash_mask_u8(int64_t F, int64_t S, const int32_t *items, const float *item_p, uint64_t seed, uint64_t call, uint8_t *out,
+                         arl_stream_t stream);
+int arl_gan_threshold_f32(const float *Y, int64_t F, int64_t S, float thr, const int64_t *out_ptr, int64_t *counts, int32_t *out_col,
+                          arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Item-table exchange of the user-sharded step (no reference counterpart: main.py:19 pins one device).
  * One process per GPU.  arl_comm_unique_id (rank 0) -> the 128 bytes travel to every rank by any side channel (torch.distributed
  * broadcast) -> arl_comm_init on every rank.  arl_allreduce_item_f32 sum-all-reduces buf[0, n_elems) IN PLACE, asynchronously on `stream`,
