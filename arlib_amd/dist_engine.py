@@ -273,30 +273,22 @@ class ShardedPropagationEngine:
         """Propagated tables for the local users and all items: mean(E_0..E_L) (recommender/LightGCN.py:230-240)."""
         if self.skip0:
             raise ValueError('forward()/step()/step_sparse() are the LightGCN mean over layers 0..L; a skip_layer0 engine uses step_simgcl()')
-        L = self.L
-        cur, nxt = self.Ea, self.Eb
-        self._hop(self.E0, cur)
-        torch.add(self.E0, cur, out=self.S)
-        for _ in range(L - 1):
-            self._hop(cur, nxt)
-            self.S.add_(nxt)
-            cur, nxt = nxt, cur
-        self.S.mul_(1.0 / (L + 1))
-        return self.S
+        return self.forward_mean()
 
     def forward_mean(self):
         """forward() for either encoder family: mean of layers 0..L (LightGCN) or 1..L (skip_layer0: SimGCL, unperturbed)."""
-        if not self.skip0:
-            return self.forward()
         L = self.L
         cur, nxt = self.Ea, self.Eb
         self._hop(self.E0, cur)
-        self.S.copy_(cur)
+        if self.skip0:
+            self.S.copy_(cur)
+        else:
+            torch.add(self.E0, cur, out=self.S)
         for _ in range(L - 1):
             self._hop(cur, nxt)
             self.S.add_(nxt)
             cur, nxt = nxt, cur
-        self.S.mul_(1.0 / L)
+        self.S.mul_(1.0 / (L if self.skip0 else L + 1))
         return self.S
 
     def backward_mean(self, G):
@@ -446,7 +438,7 @@ class ShardedPropagationEngine:
 
     def step(self, u, p, n):
         """One training iteration on the GLOBAL batch (device int32 tensors, identical on every rank)."""
-        k, L, Ul = self.k, self.L, self.Ul
+        k, Ul = self.k, self.Ul
         B = u.numel()
         out = self.forward()
         lu, lp, ln = self._local_batch(u, p, n)
@@ -465,17 +457,8 @@ class ShardedPropagationEngine:
         # backward, Horner form.  The user-side hop gathers ITEM rows of its operand, so G's item rows (per-rank partials:
         # each rank saw only its own samples) must be complete first: one more I x d all-reduce, after which G is
         # replicated on the item side and is added after each hop's reduction.
-        self.comm.all_reduce(self.G[Ul:])
+        acc = self.backward_mean(self.G)
         self.t += 1
-        acc = self.G
-        bufs = [self.Ea, self.Eb]
-        s = 1.0 / (L + 1)
-        for h in range(L):
-            last = h == L - 1
-            dst = bufs[h % 2]
-            a = s if last else 1.0
-            self._hop(acc, dst, a, a, self.G, z_partial=False)
-            acc = dst
         if hasattr(k, 'adam_dense'):
             k.adam_dense(self.E0, acc, self.m, self.v, self.lr, self.t, self.betas, self.eps)
         return self.loss_out

@@ -78,7 +78,15 @@ class PropagationEngine:
             self.S = self.E0
         self.t = 0
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=self.device)
-        self._ws = None
+        # state that later steps fill in (nothing below allocates device memory here)
+        self._G_dirty = True                        # the sparse steps keep G all-zero between calls; dense users leave it dirty
+        self._noise_seed, self._noise_stream = None, 0      # in-kernel noise (SimGCL family) / dropout masks (SSL4Rec): see _streams()
+        self.nsplit = 32            # edge ranges per batch row in the row-subset hop (cfg2 sweep: 8: 0.56 ms, 16: 0.33, 32/64: 0.21, 128: 0.36)
+        self.flags = self.bits = self.dup_bits = self.hops = None                                   # node-sized, _sparse_buffers()
+        self._sparse_B, self._sb_cache = None, {}
+        self.Gc = self.out_c = self.rows_ws = self.ar = self.arB = self._ws = None                 # batch-sized, _sparse_buffers()
+        self._sgl_acc = self._sgl_hops = None       # step_sgl()
+        self.ngcf_W = self.ngcf_m = self.ngcf_v = None      # init_ngcf()
 
     # views with the reference's names
     @property
@@ -128,25 +136,19 @@ class PropagationEngine:
         L, A = self.L, self.A
         if L == 0:
             return G
-        out = self.Ea if out is None else out
+        acc, dst = self._dense_hops(G)
         if self.skip0:
-            acc = G
-            bufs = [self.Ea, self.Eb]
-            for k in range(L - 1):
-                dst = bufs[k % 2]
-                ops.spmm(A, acc, 1.0, 1.0, G, out=dst)
-                acc = dst
-            dst = self.Eb if acc is self.Ea else self.Ea
             return ops.spmm(A, acc, 1.0 / L, out=dst)
-        acc = G
-        bufs = [self.Ea, self.Eb]
-        for k in range(L):
-            last = k == L - 1
-            s = 1.0 / (L + 1) if last else 1.0
-            dst = bufs[k % 2]
-            ops.spmm(A, acc, s, s, G, out=dst)
-            acc = dst
-        return acc
+        s = 1.0 / (L + 1)
+        return ops.spmm(A, acc, s, s, G, out=dst)
+
+    def _dense_hops(self, G):
+        """The first L-1 hops of the dense Horner backward, acc = G; acc = G + A acc, ping-pong over Ea / Eb.  Returns (acc, the buffer the
+        last hop may write): that hop, with its scale and its share of G, is the caller's."""
+        acc, bufs = G, (self.Ea, self.Eb)
+        for k in range(self.L - 1):
+            acc = ops.spmm(self.A, acc, 1.0, 1.0, G, out=bufs[k % 2])
+        return acc, bufs[(self.L - 1) % 2]
 
     def adjacency_gradient(self, G, out=None, noises=None, eps=0.1):
         """dL/d(values of A) from dL/d(out) = G for out = mean of the layers E_k, E_{k+1} = A E_k (+ a perturbation that carries no gradient when
@@ -169,30 +171,83 @@ class PropagationEngine:
             raise ValueError('forward_rows: LightGCN mean over layers 0..L with 1 <= L <= 8')
         n = rows.numel()
         self._sparse_buffers(max(n // 3, 1) if n % 3 == 0 else n)          # node-sized buffers (flags, bits, hops); batch-sized ones are not used here
-        layers = [self.E0]
-        for k in range(L - 1):
-            ops.spmm(A, layers[-1], out=self.hops[k])
-            layers.append(self.hops[k])
-        return ops.spmm_rows(A, layers[-1], rows, layers, 1.0 / (L + 1), nsplit=self.nsplit, check_range=False)
+        return self._mean_rows(A, self.hops, rows)
 
     def backward_rows(self, rows, g_rows):
         """dL/dE0 [N, d] from dL/d(forward_rows(rows)) = g_rows: scatter into the (all-zero) gradient table, flag-masked first hop, Horner
         over the remaining hops; the sparse state is cleared again before returning."""
         L, A = self.L, self.A
         s = 1.0 / (L + 1)
-        if getattr(self, '_G_dirty', True):
+        self._begin_sparse(self._sparse_B)                      # the buffers forward_rows() left current
+        self._set_rows(rows, g_rows.contiguous())
+        acc, bits = self._masked_hops(A, self.hops)
+        out = ops.spmm_flagged(A, acc, bits, s, s, self.G, self.flags)
+        self._clear_rows(rows)
+        return out
+
+    # ---- the parts of the sparse-batch schedule, each written once; the step_* methods below are these plus their own losses and perturbations
+    def _begin_sparse(self, B):
+        """Every sparse step opens with this: the buffers for batch size B current, G all-zero (it stays so between sparse steps: each clears
+        the rows it set; a dense step in between leaves it dirty)."""
+        self._sparse_buffers(B)
+        if self._G_dirty:
             self.G.zero_()
             self._G_dirty = False
-        ops.batch_rows_set_(self.G, self.flags, self.bits, rows, g_rows.contiguous(), 1.0, check_range=False, dup_bits=self.dup_bits)
-        if L == 1:
-            out = ops.spmm_flagged(A, self.G, self.bits, s, s, self.G, self.flags)
-        else:
-            acc = ops.spmm_flagged(A, self.G, self.bits, 1.0, 1.0, self.G, self.flags, out=self.hops[0])
-            for k in range(1, L - 1):
-                acc = ops.spmm_flagged(A, acc, None, 1.0, 1.0, self.G, self.flags, out=self.hops[k % 2 if len(self.hops) == 2 else k])
-            out = ops.spmm_flagged(A, acc, None, s, s, self.G, self.flags)
+
+    def _batch_rows(self, u, p, n):
+        """Node ids of the BPR rows: [0,B) users, [B,2B) positives, [2B,3B) negatives."""
+        return torch.cat([u, p + self.U, n + self.U])
+
+    def _contrast_rows(self, u, p):
+        """(node ids of the batch's unique users followed by its unique positive items, number of users among them): the InfoNCE rows."""
+        uidx = torch.unique(u.long())
+        iidx = torch.unique(p.long()) + self.U
+        return torch.cat([uidx, iidx]).to(torch.int32), uidx.numel()
+
+    def _streams(self, n):
+        """(seed, first of n consecutive stream numbers) for this step's in-kernel random draws (SimGCL-family noise, SSL4Rec dropout masks; an
+        engine runs one family or the other).  The seed is taken once from torch's global generator, by the first step that needs it."""
+        if self._noise_seed is None:
+            self._noise_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            self._noise_stream = 0
+        first = self._noise_stream
+        self._noise_stream += n
+        return self._noise_seed, first
+
+    def _mean_rows(self, graph, hops, rows, out=None, workspace=None):
+        """mean(E_0 .. E_L)[rows] over `graph`: L-1 full hops into hops[0..L-2], the last hop on the listed rows only."""
+        layers = [self.E0]
+        for k in range(self.L - 1):
+            layers.append(ops.spmm(graph, layers[-1], out=hops[k]))
+        return ops.spmm_rows(graph, layers[-1], rows, layers, 1.0 / (self.L + 1), nsplit=self.nsplit, out=out, workspace=workspace, check_range=False)
+
+    def _bpr_compact(self, out_c, B):
+        """BPR + L2 on compact batch rows ([0,B) users, [B,2B) positives, [2B,3B) negatives of out_c): loss_out and the per-sample gradients Gc."""
+        self.Gc.zero_()
+        ops.bpr_l2_fwd_bwd(out_c, B, self.ar, self.ar, self.arB, self.reg, self.Gc, workspace=self._ws, loss_out=self.loss_out, check_range=False, distinct_rows=True)
+
+    def _set_rows(self, rows, grad):
+        ops.batch_rows_set_(self.G, self.flags, self.bits, rows, grad, 1.0, check_range=False, dup_bits=self.dup_bits)      # duplicates accumulate in order; rows marked
+
+    def _mark_rows(self, rows):
+        ops.mark_rows_(self.flags, rows, 1, check_range=False)
+        ops.mark_bits_(self.bits, rows, True, self.N, check_range=False)
+
+    def _clear_rows(self, rows):
         ops.batch_rows_clear_(self.G, self.flags, self.bits, rows, check_range=False, dup_bits=self.dup_bits)
-        return out
+
+    def _masked_hops(self, graph, bufs, src=None, after_hop=None):
+        """The first L-1 hops of the masked Horner backward over the rows set / marked in G: acc = src (G itself unless given); acc = G + A acc,
+        the first hop gathering flagged rows only (bits), G read through the flags everywhere, hop k written to bufs[k % len(bufs)] (one buffer
+        per hop, or two that take turns).  after_hop(level, acc): called after the hop that produced level L-1 .. 1 (XSimGCL's injection).
+        Returns (acc, xflags) for the LAST hop, which is the caller's: with L == 1 that is still (src, bits)."""
+        acc, bits = self.G if src is None else src, self.bits
+        for k in range(self.L - 1):
+            acc = ops.spmm_flagged(graph, acc, bits, 1.0, 1.0, self.G, self.flags, out=bufs[k % len(bufs)])
+            bits = None
+            if after_hop is not None:
+                after_hop(self.L - 1 - k, acc)
+        return acc, bits
 
     def loss_and_grad_out(self, out, u, p, n):
         self.G.zero_()
@@ -229,35 +284,24 @@ class PropagationEngine:
         L, A = self.L, self.A
         B = u.numel()
         if rows is None:
-            rows = torch.cat([u, p + self.U, n + self.U])
-        self._sparse_buffers(B)
-        if getattr(self, '_G_dirty', True):
-            self.G.zero_()
-            self._G_dirty = False
+            rows = self._batch_rows(u, p, n)
+        self._begin_sparse(B)
         s = 1.0 / (L + 1)
-        # forward: L-1 full hops, last hop on the batch rows
-        layers = [self.E0]
-        for k in range(L - 1):
-            ops.spmm(A, layers[-1], out=self.hops[k])
-            layers.append(self.hops[k])
-        ops.spmm_rows(A, layers[-1], rows, layers, s, nsplit=self.nsplit, out=self.out_c, workspace=self.rows_ws, check_range=False)
-        # loss + compact per-sample gradients (rows [0,B) users, [B,2B) positives, [2B,3B) negatives of out_c)
-        self.Gc.zero_()
-        ops.bpr_l2_fwd_bwd(self.out_c, B, self.ar, self.ar, self.arB, self.reg, self.Gc, workspace=self._ws, loss_out=self.loss_out, check_range=False, distinct_rows=True)
+        # forward: L-1 full hops, last hop on the batch rows; loss + compact per-sample gradients
+        self._mean_rows(A, self.hops, rows, out=self.out_c, workspace=self.rows_ws)
+        self._bpr_compact(self.out_c, B)
         if extra_grad is not None:
             extra_grad()
-        ops.batch_rows_set_(self.G, self.flags, self.bits, rows, self.Gc, 1.0, check_range=False, dup_bits=self.dup_bits)      # duplicates accumulate in order; rows marked
-        # backward (Horner): first hop gathers flagged rows only; G is read through the flags everywhere
+        self._set_rows(rows, self.Gc)
+        # backward (Horner): first hop gathers flagged rows only; G is read through the flags everywhere; Adam is the last hop's epilogue
         self.t += 1
+        acc, bits = self._masked_hops(A, self.hops)
         if L == 1:
-            ops.spmm_flagged(A, self.G, self.bits, s, s, self.G, self.flags, out=self.hops[0])
+            ops.spmm_flagged(A, acc, bits, s, s, self.G, self.flags, out=self.hops[0])
             ops.adam_dense(self.E0, self.hops[0], self.m, self.v, self.lr, self.t, self.betas, self.eps)
         else:
-            acc = ops.spmm_flagged(A, self.G, self.bits, 1.0, 1.0, self.G, self.flags, out=self.hops[0])
-            for k in range(1, L - 1):
-                acc = ops.spmm_flagged(A, acc, None, 1.0, 1.0, self.G, self.flags, out=self.hops[k % 2 if len(self.hops) == 2 else k])
             ops.spmm_adam(A, acc, s, s, self.G, self.E0, self.m, self.v, self.lr, self.t, self.betas, self.eps, zflags=self.flags)
-        ops.batch_rows_clear_(self.G, self.flags, self.bits, rows, check_range=False, dup_bits=self.dup_bits)
+        self._clear_rows(rows)
         return self.loss_out
 
     def step_ssl4rec(self, u, p, n, cl_rate=1.0, tau=0.2, drop=0.2, masks=None, seed=None, stream_id=None):
@@ -276,11 +320,7 @@ class PropagationEngine:
         if masks is not None and tuple(masks.shape) != (2, 2, B, self.d):
             raise ValueError('step_ssl4rec: masks [2, 2, B, d]')
         if seed is None:
-            if getattr(self, '_mask_seed', None) is None:
-                self._mask_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                self._mask_stream = 0
-            seed, stream_id = self._mask_seed, self._mask_stream
-            self._mask_stream += 1
+            seed, stream_id = self._streams(1)
         cl = []
         def contrastive():
             loss, _ = ops.ssl_dropout_nce(self.out_c[:B], self.out_c[B:2 * B], drop, tau, G=(self.Gc[:B], self.Gc[B:2 * B]), upstream=cl_rate,
@@ -307,15 +347,12 @@ class PropagationEngine:
         """capture: optional dict; receives the table gradient ('table') and the weight gradients ('W') of this step (diagnostics / tests:
         the Adam update then runs as a separate dense launch instead of the last hop's epilogue -- same numbers)."""
         L, A, d = self.L, self.A, self.d
-        if L < 1 or not hasattr(self, 'ngcf_W') or d not in ops.NGCF_DENSE_WIDTHS:
+        if L < 1 or self.ngcf_W is None or d not in ops.NGCF_DENSE_WIDTHS:
             raise ValueError('step_ngcf: needs n_layers >= 1, init_ngcf() and d in %s' % (ops.NGCF_DENSE_WIDTHS,))
         B = u.numel()
         if rows is None:
-            rows = torch.cat([u, p + self.U, n + self.U])
-        self._sparse_buffers(B)
-        if getattr(self, '_G_dirty', True):
-            self.G.zero_()
-            self._G_dirty = False
+            rows = self._batch_rows(u, p, n)
+        self._begin_sparse(B)
         s = 1.0 / (L + 1)
         Wcat = [torch.cat([a, b], 0) for a, b in self.ngcf_W]
         # forward: L-1 full layers, the last one on the batch rows
@@ -334,17 +371,16 @@ class PropagationEngine:
         for e in egos[:-1]:
             acc += ops.gather_rows(e, rows, check_range=False)
         acc *= s
-        self.Gc.zero_()
-        ops.bpr_l2_fwd_bwd(acc, B, self.ar, self.ar, self.arB, self.reg, self.Gc, workspace=self._ws, loss_out=self.loss_out, check_range=False, distinct_rows=True)
+        self._bpr_compact(acc, B)
         Gs = self.Gc * s                                         # every layer's batch rows receive this share of dL/d(out) directly
         # backward
         self.t += 1
         gP_r, gE_r, gW = ops.ngcf_dense_bwd(Gs, out_r, P_r, E_r, Wcat[L - 1], slope)
         gWs = [None] * L
         gWs[L - 1] = gW
-        ops.batch_rows_set_(self.G, self.flags, self.bits, rows, gP_r, 1.0, check_range=False, dup_bits=self.dup_bits)
+        self._set_rows(rows, gP_r)
         g = ops.spmm_flagged(A, self.G, self.bits)              # A^T (rows' gP scattered) = A (...), A symmetric
-        ops.batch_rows_clear_(self.G, self.flags, self.bits, rows, check_range=False, dup_bits=self.dup_bits)
+        self._clear_rows(rows)
         ops.scatter_add_rows(g, rows, gE_r + Gs, 1.0, check_range=False)
         if L == 1:
             if capture is not None:
@@ -383,36 +419,27 @@ class PropagationEngine:
         stream per hop and view (the reference's rand_like calls).  Returns (loss_out, cl_loss) device tensors."""
         if not self.skip0 or self.optimizer != 'adam':
             raise ValueError('step_simgcl needs a skip_layer0 engine with Adam')
-        L, A, U, N, d = self.L, self.A, self.U, self.N, self.d
+        L, A = self.L, self.A
         B = u.numel()
-        self._sparse_buffers(B)
-        if getattr(self, '_G_dirty', True):
-            self.G.zero_(); self._G_dirty = False
+        self._begin_sparse(B)
         inv = 1.0 / L
-        rows = torch.cat([u, p + U, n + U])
-        uidx = torch.unique(u.long())
-        iidx = torch.unique(p.long()) + U
-        rows_cl = torch.cat([uidx, iidx]).to(torch.int32)
-        nu = uidx.numel()
+        rows = self._batch_rows(u, p, n)
+        rows_cl, nu = self._contrast_rows(u, p)
         # noise: injected tables (parity tests) or, by default, drawn inside the perturbation kernel from a seed taken once from torch's global
         # generator and a running stream number -- one "draw" per hop and view like the reference's rand_like calls, but no [N, d] noise table,
         # no clone of the operand, and the compact last-hop rows get exactly the values a full-table draw would have given them
         rng_mode = noises is None
         if rng_mode:
-            if getattr(self, '_noise_seed', None) is None:
-                self._noise_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                self._noise_stream = 0
-            stream0 = self._noise_stream
-            self._noise_stream += 2 * L
+            seed, stream0 = self._streams(2 * L)
         rnd = (lambda v, k: noises[v][k]) if noises is not None else None
         def perturb_full(src, v, k, out=None):                          # hop-k table of view v
             if rng_mode:
-                return ops.simgcl_perturb_rng(src, eps, self._noise_seed, stream0 + v * L + k, out=out)
+                return ops.simgcl_perturb_rng(src, eps, seed, stream0 + v * L + k, out=out)
             dst = src.clone() if out is None else out.copy_(src)
             return ops.simgcl_perturb_(dst, rnd(v, k), eps)
         def perturb_rows(src, v, k, sel):                               # compact rows `sel` of the hop-k table of view v, in place
             if rng_mode:
-                return ops.simgcl_perturb_rng(src, eps, self._noise_seed, stream0 + v * L + k, out=src, row_ids=sel)
+                return ops.simgcl_perturb_rng(src, eps, seed, stream0 + v * L + k, out=src, row_ids=sel)
             return ops.simgcl_perturb_(src, rnd(v, k)[sel.long()].contiguous(), eps)
         # ---- forwards
         E1 = ops.spmm(A, self.E0, out=self.hops[0])                       # shared first hop
@@ -434,8 +461,7 @@ class PropagationEngine:
                 last += ops.gather_rows(t, sel, check_range=False)
             return last * inv
         out_c = finish(E1, None)
-        self.Gc.zero_()
-        ops.bpr_l2_fwd_bwd(out_c, B, self.ar, self.ar, self.arB, self.reg, self.Gc, workspace=self._ws, loss_out=self.loss_out, check_range=False, distinct_rows=True)
+        self._bpr_compact(out_c, B)
         ops.scatter_add_rows(self.G, rows, self.Gc, 1.0, check_range=False)
         views = []
         for v in (0, 1):
@@ -447,21 +473,16 @@ class PropagationEngine:
         gcl = torch.cat([du1 + du2, di1 + di2], 0)                         # both views differentiate through the same operator
         ops.scatter_add_rows(self.G, rows_cl, gcl, cl_rate, check_range=False)
         allrows = torch.cat([rows, rows_cl])
-        ops.mark_rows_(self.flags, allrows, 1, check_range=False)
-        ops.mark_bits_(self.bits, allrows, True, N, check_range=False)
+        self._mark_rows(allrows)
         # ---- one backward pass: acc = G; (L-1) x: acc = G + A acc; g = A acc / L
         self.t += 1
-        acc, first = self.G, True
-        for k in range(L - 1):
-            dst = self.hops[1] if acc is not self.hops[1] else self.hops[0]
-            ops.spmm_flagged(A, acc, self.bits if first else None, 1.0, 1.0, self.G, self.flags, out=dst)
-            acc, first = dst, False
-        if first:       # L == 1: the only hop gathers the sparse G itself
-            tmp = ops.spmm_flagged(A, self.G, self.bits, inv, 0.0, None, None, out=self.hops[1])
+        acc, bits = self._masked_hops(A, (self.hops[1], self.hops[0]))
+        if L == 1:      # the only hop gathers the sparse G itself
+            tmp = ops.spmm_flagged(A, acc, bits, inv, 0.0, None, None, out=self.hops[1])
             ops.adam_dense(self.E0, tmp, self.m, self.v, self.lr, self.t, self.betas, self.eps)
         else:
             ops.spmm_adam(A, acc, inv, 0.0, None, self.E0, self.m, self.v, self.lr, self.t, self.betas, self.eps)
-        ops.batch_rows_clear_(self.G, self.flags, self.bits, allrows, check_range=False, dup_bits=self.dup_bits)
+        self._clear_rows(allrows)
         return self.loss_out, cl_loss
 
     def step_xsimgcl(self, u, p, n, cl_rate=0.2, tau=0.1, eps=0.1, layer_cl=1, noises=None):
@@ -474,39 +495,30 @@ class PropagationEngine:
         per hop (the reference's rand_like).  Returns (loss_out, cl_loss)."""
         if not self.skip0 or self.optimizer != 'adam':
             raise ValueError('step_xsimgcl needs a skip_layer0 engine with Adam')
-        L, A, U, N, d = self.L, self.A, self.U, self.N, self.d
+        L, A = self.L, self.A
         if not (1 <= layer_cl <= L):
             raise ValueError('layer_cl must be in [1, L]')
         B = u.numel()
-        self._sparse_buffers(B)
-        if getattr(self, '_G_dirty', True):
-            self.G.zero_(); self._G_dirty = False
+        self._begin_sparse(B)
         inv = 1.0 / L
-        rows = torch.cat([u, p + U, n + U])
-        uidx = torch.unique(u.long())
-        iidx = torch.unique(p.long()) + U
-        rows_cl = torch.cat([uidx, iidx]).to(torch.int32)
-        nu = uidx.numel()
+        rows = self._batch_rows(u, p, n)
+        rows_cl, nu = self._contrast_rows(u, p)
         sel = torch.cat([rows, rows_cl])                                    # compact rows: [0,3B) BPR, then the CL rows
         rng_mode = noises is None                                           # default: noise drawn inside the perturbation kernel (step_simgcl)
         if rng_mode:
-            if getattr(self, '_noise_seed', None) is None:
-                self._noise_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                self._noise_stream = 0
-            stream0 = self._noise_stream
-            self._noise_stream += L
+            seed, stream0 = self._streams(L)
         # ---- forward
         layers, cur = [], self.E0
         for k in range(L - 1):
-            nxt = ops.spmm(A, cur, out=self.hops[k % len(self.hops)] if L <= 3 else None)
+            nxt = ops.spmm(A, cur, out=self.hops[k] if L <= 3 else None)
             if rng_mode:
-                ops.simgcl_perturb_rng(nxt, eps, self._noise_seed, stream0 + k, out=nxt)
+                ops.simgcl_perturb_rng(nxt, eps, seed, stream0 + k, out=nxt)
             else:
                 ops.simgcl_perturb_(nxt, noises[k], eps)
             layers.append(nxt); cur = nxt
         last = ops.spmm_rows(A, cur, sel, (), 1.0, nsplit=self.nsplit, check_range=False)
         if rng_mode:
-            ops.simgcl_perturb_rng(last, eps, self._noise_seed, stream0 + L - 1, out=last, row_ids=sel)
+            ops.simgcl_perturb_rng(last, eps, seed, stream0 + L - 1, out=last, row_ids=sel)
         else:
             ops.simgcl_perturb_(last, noises[L - 1][sel.long()].contiguous(), eps)
         mean_c = last.clone()
@@ -515,9 +527,7 @@ class PropagationEngine:
         mean_c *= inv
         cl_c = last[3 * B:] if layer_cl == L else ops.gather_rows(layers[layer_cl - 1], rows_cl, check_range=False)
         # ---- losses and compact gradients
-        self.Gc.zero_()
-        ops.bpr_l2_fwd_bwd(mean_c[:3 * B].contiguous(), B, self.ar, self.ar, self.arB, self.reg, self.Gc, workspace=self._ws, loss_out=self.loss_out,
-                           check_range=False, distinct_rows=True)
+        self._bpr_compact(mean_c[:3 * B].contiguous(), B)
         mcl = mean_c[3 * B:]
         lu, du1, du2 = ops.infonce_fwd_bwd(mcl[:nu].contiguous(), cl_c[:nu].contiguous(), tau)
         li, di1, di2 = ops.infonce_fwd_bwd(mcl[nu:].contiguous(), cl_c[nu:].contiguous(), tau)
@@ -527,36 +537,25 @@ class PropagationEngine:
         # G <- G_mean / L  (sparse rows; G is all-zero between steps)
         ops.scatter_add_rows(self.G, rows, self.Gc, inv, check_range=False)
         ops.scatter_add_rows(self.G, rows_cl, g_mean_cl, cl_rate * inv, check_range=False)
-        allrows = sel
-        ops.mark_rows_(self.flags, allrows, 1, check_range=False)
-        ops.mark_bits_(self.bits, allrows, True, N, check_range=False)
-        # ---- backward
+        self._mark_rows(sel)
+        # ---- backward: the masked Horner pass with G_cl added at level layer_cl
         self.t += 1
-        bufs = [self.hops[1], self.hops[0]] if len(self.hops) >= 2 else [torch.empty_like(self.E0), torch.empty_like(self.E0)]
+        src = self.G
+        if layer_cl == L:                                                   # acc_L = G + G_cl: both sparse, on the same flagged rows ...
+            if L > 1:                                                       # ... on a copy when later levels add G alone
+                src = self.G.clone()
+            ops.scatter_add_rows(src, rows_cl, g_layer, 1.0, check_range=False)
+        def inject(level, acc):
+            if level == layer_cl:
+                ops.scatter_add_rows(acc, rows_cl, g_layer, 1.0, check_range=False)
+        bufs = (self.hops[1], self.hops[0])
+        acc, bits = self._masked_hops(A, bufs, src, inject)
         if L == 1:
-            src = self.G
-            if layer_cl == 1:                                               # acc_1 = G + G_cl: both sparse, on the same flagged rows
-                ops.scatter_add_rows(self.G, rows_cl, g_layer, 1.0, check_range=False)
-            tmp = ops.spmm_flagged(A, src, self.bits, 1.0, 0.0, None, None, out=bufs[0])
+            tmp = ops.spmm_flagged(A, acc, bits, 1.0, 0.0, None, None, out=bufs[0])
             ops.adam_dense(self.E0, tmp, self.m, self.v, self.lr, self.t, self.betas, self.eps)
         else:
-            if layer_cl == L:                                               # acc_L = G + G_cl (sparse); later levels add G alone
-                first_src = self.G.clone()
-                ops.scatter_add_rows(first_src, rows_cl, g_layer, 1.0, check_range=False)
-            else:
-                first_src = self.G
-            acc = ops.spmm_flagged(A, first_src, self.bits, 1.0, 1.0, self.G, self.flags, out=bufs[0])       # level L-1
-            level = L - 1
-            while True:
-                if level == layer_cl:
-                    ops.scatter_add_rows(acc, rows_cl, g_layer, 1.0, check_range=False)
-                if level == 1:
-                    break
-                dst = bufs[1] if acc is bufs[0] else bufs[0]
-                acc = ops.spmm_flagged(A, acc, None, 1.0, 1.0, self.G, self.flags, out=dst)
-                level -= 1
             ops.spmm_adam(A, acc, 1.0, 0.0, None, self.E0, self.m, self.v, self.lr, self.t, self.betas, self.eps)
-        ops.batch_rows_clear_(self.G, self.flags, self.bits, allrows, check_range=False, dup_bits=self.dup_bits)
+        self._clear_rows(sel)
         return self.loss_out, cl_loss
 
     def step_sgl(self, u, p, n, view1, view2, cl_rate=0.2, tau=0.2):
@@ -567,53 +566,38 @@ class PropagationEngine:
         instead of the 6L of three autograd passes.  Returns (loss_out, cl_loss)."""
         if self.skip0 or self.optimizer != 'adam' or self.L < 1:
             raise ValueError('step_sgl needs a LightGCN-style engine (layers 0..L averaged) with Adam')
-        L, U, N, d = self.L, self.U, self.N, self.d
+        L = self.L
         B = u.numel()
-        self._sparse_buffers(B)
-        if getattr(self, '_G_dirty', True):
-            self.G.zero_(); self._G_dirty = False
+        self._begin_sparse(B)
         s = 1.0 / (L + 1)
-        rows = torch.cat([u, p + U, n + U])
-        rows_cl = torch.cat([torch.unique(u.long()), torch.unique(p.long()) + U]).to(torch.int32)
-        if not hasattr(self, '_sgl_acc'):
+        rows = self._batch_rows(u, p, n)
+        rows_cl, _ = self._contrast_rows(u, p)
+        if self._sgl_acc is None:
             self._sgl_acc = torch.empty_like(self.E0)
             self._sgl_hops = [torch.empty_like(self.E0) for _ in range(max(L - 1, 1))]
 
-        def forward_rows(graph, sel):                                        # mean of layers 0..L at the rows `sel`
-            layers = [self.E0]
-            for k in range(L - 1):
-                layers.append(ops.spmm(graph, layers[-1], out=self._sgl_hops[k]))
-            return ops.spmm_rows(graph, layers[-1], sel, layers, s, nsplit=self.nsplit, check_range=False)
-
-        def backward_into(graph, sel, grad_c, dst, accumulate):             # dst (+)= dL/dE0 of a pass whose output gradient is grad_c at rows sel
-            ops.batch_rows_set_(self.G, self.flags, self.bits, sel, grad_c, 1.0, check_range=False, dup_bits=self.dup_bits)
-            beta, Z = (1.0, dst) if accumulate else (0.0, None)
-            if L == 1:
-                tmp = ops.spmm_flagged(graph, self.G, self.bits, s, s, self.G, self.flags, out=self._sgl_hops[0])
-            else:
-                acc = ops.spmm_flagged(graph, self.G, self.bits, 1.0, 1.0, self.G, self.flags, out=self._sgl_hops[0])
-                for k in range(1, L - 1):
-                    acc = ops.spmm_flagged(graph, acc, None, 1.0, 1.0, self.G, self.flags, out=self._sgl_hops[k])
-                tmp = ops.spmm_flagged(graph, acc, None, s, s, self.G, self.flags, out=self.hops[0])
+        def backward_into(graph, sel, grad_c, accumulate):                  # _sgl_acc (+)= dL/dE0 of a pass whose output gradient is grad_c at rows sel
+            self._set_rows(sel, grad_c)
+            acc, bits = self._masked_hops(graph, self._sgl_hops)
+            tmp = ops.spmm_flagged(graph, acc, bits, s, s, self.G, self.flags, out=self._sgl_hops[0] if L == 1 else self.hops[0])
             if accumulate:
-                dst.add_(tmp)
+                self._sgl_acc.add_(tmp)
             else:
-                dst.copy_(tmp)
-            ops.batch_rows_clear_(self.G, self.flags, self.bits, sel, check_range=False, dup_bits=self.dup_bits)
+                self._sgl_acc.copy_(tmp)
+            self._clear_rows(sel)
 
         # clean pass: BPR + L2 on the batch rows
-        out_c = forward_rows(self.A, rows)
-        self.Gc.zero_()
-        ops.bpr_l2_fwd_bwd(out_c, B, self.ar, self.ar, self.arB, self.reg, self.Gc, workspace=self._ws, loss_out=self.loss_out, check_range=False, distinct_rows=True)
+        out_c = self._mean_rows(self.A, self._sgl_hops, rows)
+        self._bpr_compact(out_c, B)
         # the two views at the contrastive rows, one InfoNCE over users and items together
-        v1 = forward_rows(view1, rows_cl)
-        v2 = forward_rows(view2, rows_cl)
+        v1 = self._mean_rows(view1, self._sgl_hops, rows_cl)
+        v2 = self._mean_rows(view2, self._sgl_hops, rows_cl)
         lcl, d1, d2 = ops.infonce_fwd_bwd(v1, v2, tau)
         cl_loss = cl_rate * lcl[0]
         # backward: three passes into one gradient table, then Adam
-        backward_into(self.A, rows, self.Gc, self._sgl_acc, False)
-        backward_into(view1, rows_cl, d1 * cl_rate, self._sgl_acc, True)
-        backward_into(view2, rows_cl, d2 * cl_rate, self._sgl_acc, True)
+        backward_into(self.A, rows, self.Gc, False)
+        backward_into(view1, rows_cl, d1 * cl_rate, True)
+        backward_into(view2, rows_cl, d2 * cl_rate, True)
         self.t += 1
         ops.adam_dense(self.E0, self._sgl_acc, self.m, self.v, self.lr, self.t, self.betas, self.eps)
         return self.loss_out, cl_loss
@@ -621,27 +605,24 @@ class PropagationEngine:
     def _sparse_buffers(self, B):
         """Buffers of the sparse-batch step.  The node-sized ones exist once; the batch-sized ones are kept per batch size (an epoch has two:
         the full batches and the last one), so that the last batch of every epoch does not re-allocate them."""
-        if getattr(self, '_sparse_B', None) == B:
+        if self._sparse_B == B:
             return
         dev, d = self.device, self.d
-        if not hasattr(self, '_sb_cache'):
-            self._sb_cache = {}
+        if self.flags is None:
             self.flags = torch.zeros(self.N, dtype=torch.uint8, device=dev)          # byte per row: read once per OUTPUT row (epilogue)
             self.bits = torch.zeros((self.N + 31) // 32, dtype=torch.int32, device=dev)   # bit per node: read once per EDGE (masked hop)
             self.dup_bits = torch.zeros_like(self.bits)                                   # rows a batch names more than once (ordered accumulation)
-            self.nsplit = 32            # edge ranges per batch row in the row-subset hop (cfg2 sweep: 8: 0.56 ms, 16: 0.33, 32/64: 0.21, 128: 0.36)
             # forward needs E_1..E_{L-1} alive at the same time; Ea/Eb cover L <= 3
             self.hops = [self.Ea, self.Eb] + [torch.empty_like(self.Ea) for _ in range(max(0, self.L - 3))]
         sb = self._sb_cache.get(B)
         if sb is None:
             ar = torch.arange(B, dtype=torch.int32, device=dev)
-            sb = {'Gc': torch.zeros(3 * B, d, dtype=torch.float32, device=dev), 'out_c': torch.empty(3 * B, d, dtype=torch.float32, device=dev),
-                  'rows_ws': torch.empty(3 * B * self.nsplit * d, dtype=torch.float32, device=dev), 'ar': ar, 'arB': ar + B,
-                  '_ws': torch.empty(4 * B, dtype=torch.float32, device=dev)}
+            sb = (torch.zeros(3 * B, d, dtype=torch.float32, device=dev), torch.empty(3 * B, d, dtype=torch.float32, device=dev),
+                  torch.empty(3 * B * self.nsplit * d, dtype=torch.float32, device=dev), ar, ar + B, torch.empty(4 * B, dtype=torch.float32, device=dev))
             if len(self._sb_cache) >= 8:                   # unusual callers with many batch sizes: drop the oldest set
                 del self._sb_cache[next(iter(self._sb_cache))]
             self._sb_cache[B] = sb
-        self.Gc, self.out_c, self.rows_ws, self.ar, self.arB, self._ws = sb['Gc'], sb['out_c'], sb['rows_ws'], sb['ar'], sb['arB'], sb['_ws']
+        self.Gc, self.out_c, self.rows_ws, self.ar, self.arB, self._ws = sb
         self._sparse_B = B
 
     def step_dense(self, u, p, n):
@@ -651,12 +632,7 @@ class PropagationEngine:
         lo = self.loss_and_grad_out(out, u, p, n)
         self.t += 1
         if self.optimizer == 'adam' and L > 0 and not self.skip0:
-            acc = self.G
-            bufs = [self.Ea, self.Eb]
-            for k in range(L - 1):
-                dst = bufs[k % 2]
-                ops.spmm(A, acc, 1.0, 1.0, self.G, out=dst)
-                acc = dst
+            acc, _ = self._dense_hops(self.G)
             s = 1.0 / (L + 1)
             ops.spmm_adam(A, acc, s, s, self.G, self.E0, self.m, self.v, self.lr, self.t, self.betas, self.eps)
             return lo

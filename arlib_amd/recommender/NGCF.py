@@ -173,7 +173,7 @@ class NGCF(Recommender):
         fresh = not any('exp_avg' in optimizer.state[q] for q in self._params() + self._weight_params())
         super()._bind_optimizer_state(eng, optimizer, kind)
         L = self.model.layers
-        if not hasattr(eng, 'ngcf_W') or any(a.data_ptr() != self.model.W['w1_%d' % k].data_ptr() for k, (a, b) in enumerate(eng.ngcf_W)):
+        if eng.ngcf_W is None or any(a.data_ptr() != self.model.W['w1_%d' % k].data_ptr() for k, (a, b) in enumerate(eng.ngcf_W)):
             eng.init_ngcf([(self.model.W['w1_%d' % k], self.model.W['w2_%d' % k]) for k in range(L)])
         elif fresh:
             for pair in eng.ngcf_m + eng.ngcf_v:
