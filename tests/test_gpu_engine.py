@@ -162,6 +162,7 @@ def test_sparse_step_equals_dense_step(mods):
         assert rel_err(ea.E0.cpu().numpy(), eb.E0.cpu().numpy()) < RTOL, L
         assert rel_err(ea.m.cpu().numpy(), eb.m.cpu().numpy()) < RTOL and rel_err(ea.v.cpu().numpy(), eb.v.cpu().numpy()) < RTOL
         assert float(ea.G.abs().max()) == 0.0 and int(ea.flags.max()) == 0 and int(ea.bits.abs().max()) == 0       # sparse state is cleared after every step
+        assert int(ea.dup_bits.abs().max()) == 0                                                                     # the duplicate bitmap too
 
 
 @pytest.mark.parametrize('d', [32, 8, 128, 256])          # 256: one row per wave, the flag mask needs all 64 lanes (found by tools/spmm_fuzz.py)
@@ -253,7 +254,7 @@ def test_simgcl_fused_step_matches_reference(mods, ml100k):
     assert abs(cl.item() - g['cl_loss'][0]) <= RTOL * abs(g['cl_loss'][0])
     E = eng.E0.cpu().numpy()
     assert close(E[:U], g['user_k1']) and close(E[U:], g['item_k1'])
-    assert float(eng.G.abs().max()) == 0.0 and int(eng.flags.max()) == 0
+    assert float(eng.G.abs().max()) == 0.0 and int(eng.flags.max()) == 0 and int(eng.dup_bits.abs().max()) == 0
 
 
 @pytest.mark.parametrize('L,lc', [(1, 1), (3, 1), (3, 2), (3, 3)])
@@ -292,7 +293,7 @@ def test_xsimgcl_fused_step_equals_autograd_route_for_other_depths(mods, ml100k,
     lo, cl2 = eng.step_xsimgcl(u.int(), p.int(), n.int(), cl_rate=0.2, tau=0.1, eps=0.1, layer_cl=lc, noises=noise)
     assert abs(cl2.item() - cl.item()) <= RTOL * abs(cl.item())
     assert rel_err(eng.E0.cpu().numpy(), ref) < RTOL
-    assert float(eng.G.abs().max()) == 0.0 and int(eng.flags.max()) == 0
+    assert float(eng.G.abs().max()) == 0.0 and int(eng.flags.max()) == 0 and int(eng.dup_bits.abs().max()) == 0
 
 
 @pytest.mark.parametrize('L', [1, 3])
@@ -330,4 +331,4 @@ def test_sgl_fused_step_equals_autograd_route_for_other_depths(mods, ml100k, L):
     lo, cl2 = eng.step_sgl(u.int(), p.int(), n.int(), v1, v2, cl_rate=0.2, tau=0.2)
     assert abs(cl2.item() - cl.item()) <= RTOL * abs(cl.item())
     assert rel_err(eng.E0.cpu().numpy(), ref) < RTOL
-    assert float(eng.G.abs().max()) == 0.0 and int(eng.flags.max()) == 0
+    assert float(eng.G.abs().max()) == 0.0 and int(eng.flags.max()) == 0 and int(eng.dup_bits.abs().max()) == 0
