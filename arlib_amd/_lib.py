@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ARLIB_AMD_LIB') or os.path.join(_HERE, 'lib', 'libarlib_amd.so')      # override: developer builds (e.g. `make prof`)
-ABI_VERSION = 27
+ABI_VERSION = 28
 _lib = None
 
 
@@ -129,6 +129,8 @@ _SIGS = {
     'arl_gan_template_i32': (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     'arl_gan_hash_mask_u8': (C.c_int, [_i64, _i64, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
     'arl_gan_threshold_f32': (C.c_int, [_vp, _i64, _i64, _f, _vp, _vp, _vp, _vp]),
+    'arl_colsoftmax_target_workspace_bytes': (_i64, [_i64, _i64, _i64, _i32]),
+    'arl_colsoftmax_target_loss_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'arl_comm_load': (C.c_int, [C.c_char_p]),
     'arl_comm_unique_id': (C.c_int, [_vp]),
     'arl_comm_init': (C.c_int, [_vp, _i64, _i64, _i64, C.POINTER(C.c_void_p)]),

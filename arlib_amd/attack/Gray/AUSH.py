@@ -165,6 +165,10 @@ class AUSH(AttackBase):
                     self.loss_log.append(_gan.g_step(G, D, optimize_G, self._template(), T, fused))
             self.G = G
             self.D = D
+        return self._fake_profiles()
+
+    def _fake_profiles(self):
+        """The trained G on one more template, thresholded at 0.1, the targets appended to every fake row (AUSH.py:116-141)."""
         self.G.eval()
         tpl = self._template()
         Y, rowptr, col = _gan.generate(self.G, tpl, self.fused())

@@ -2052,3 +2052,8 @@ def gan_threshold(Y, thr=0.1):
     col = torch.empty(max(nnz, 1), dtype=torch.int32, device=Y.device)
     check(L.arl_gan_threshold_f32(_ptr(Y), F, S, float(thr), _ptr(rowptr), None, _ptr(col), _stream()), 'arl_gan_threshold_f32 (fill)')
     return rowptr, col[:nnz]
+
+
+# ================================================================================================ LegUP's ranking loss (csrc/arl_colsoftmax.hip)
+# (module of its own: arlib_amd/colsoftmax.py, with its poisoned-memory sweep in tests/test_gpu_legup_poison.py)
+from .colsoftmax import colsoftmax_target_supported, colsoftmax_target_loss, colsoftmax_target_loss_composed, colsoftmax_target  # noqa: E402,F401

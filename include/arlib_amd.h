@@ -587,6 +587,18 @@ int arl_gan_threshold_f32(const float *Y, int64_t F, int64_t S, float thr, const
                           arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * LegUP's ranking loss (csrc/arl_colsoftmax.hip; reference attack/Gray/LegUP.py:160-171) -- a softmax over the USERS of every item column
+ * of s = Pu Pi^T [U, I], which is never stored.  Pu [U, d], Pi [I, d], d in {16, 32, 64, 128}, 16-byte aligned; targets: T device column
+ * ids in [0, I) (1 <= T <= 1024; a repeated id counts as often as it is listed).
+ *   lse [I]  : lse[i] = log sum_u exp(s[u, i]), with a running maximum
+ *   loss [1] : -(I * sum_u sum_t s[u, c_t] - U * T * sum_i lse[i])  =  -sum_{u, t, i} (s[u, c_t] - lse[i])
+ *   dPu [U, d], dPi [I, d] (each optional, NULL = skipped): the loss's gradients.
+ * Fixed-order reductions: bit-identical from run to run.  The workspace needs no initialisation. */
+int64_t arl_colsoftmax_target_workspace_bytes(int64_t U, int64_t I, int64_t d, int32_t want_dPi);
+int arl_colsoftmax_target_loss_f32(const float *Pu, int64_t U, const float *Pi, int64_t I, int64_t d, const int32_t *targets, int64_t T, float *lse,
+                                   float *loss, float *dPu, float *dPi, void *workspace, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Item-table exchange of the user-sharded step (no reference counterpart: main.py:19 pins one device).
  * One process per GPU.  arl_comm_unique_id (rank 0) -> the 128 bytes travel to every rank by any side channel (torch.distributed
  * broadcast) -> arl_comm_init on every rank.  arl_allreduce_item_f32 sum-all-reduces buf[0, n_elems) IN PLACE, asynchronously on `stream`,
