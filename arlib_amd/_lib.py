@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ARLIB_AMD_LIB') or os.path.join(_HERE, 'lib', 'libarlib_amd.so')      # override: developer builds (e.g. `make prof`)
-ABI_VERSION = 28
+ABI_VERSION = 29
 _lib = None
 
 
@@ -49,6 +49,7 @@ _SIGS = {
     'arl_spmm_csr_layersum_f32': (C.c_int, [C.POINTER(arl_csr), _vp, _i64, _vp, _vp, _vp, _vp]),
     'arl_spmm_csr_adam_f32': (C.c_int, [C.POINTER(arl_csr), _vp, _i64, _f, _f, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i64, _vp]),
     'arl_spmm_blocked_f32': (C.c_int, [C.POINTER(arl_blocked), _vp, _i64, _f, _f, _vp, _vp, _vp, _vp]),
+    'arl_spmm_blocked_flagged_f32': (C.c_int, [C.POINTER(arl_blocked), _vp, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp]),
     'arl_spmm_csr_rscale_f32': (C.c_int, [C.POINTER(arl_csr), _vp, _i64, _vp, _f, _f, _vp, _vp, _vp]),
     'arl_spmm_blocked_rscale_f32': (C.c_int, [C.POINTER(arl_blocked), _vp, _i64, _vp, _f, _f, _vp, _vp, _vp]),
     'arl_spmm_blocked_layersum_f32': (C.c_int, [C.POINTER(arl_blocked), _vp, _i64, _vp, _vp, _vp, _vp]),
@@ -61,6 +62,8 @@ _SIGS = {
     'arl_spmm_csr_flagged_f32': (C.c_int, [C.POINTER(arl_csr), _vp, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp]),
     'arl_spmm_csr_rows_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'arl_spmm_csr_rows_f32': (C.c_int, [C.POINTER(arl_csr), _vp, _i64, _vp, _i64, _i64, _vp, _i64, _f, _vp, _vp, _vp, _vp]),
+    'arl_spmm_csr_rows_pieces_f32': (C.c_int, [C.POINTER(arl_csr), _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _f, _vp, _vp, _vp, _vp]),
+    'arl_spmm_csr_rows_scratch_offset': (_i64, [_i64, _i64, _i64]),
     'arl_mark_rows_u8': (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     'arl_mark_rows_bits_u32': (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     'arl_zero_rows_f32': (C.c_int, [_vp, _vp, _i64, _i64, _vp]),

@@ -305,6 +305,143 @@ __global__ __launch_bounds__(kBlock) void subset_finish_kernel(const float *__re
     *reinterpret_cast<float4 *>(out_c + (size_t)t * d + q * 4) = make_float4(w * a.x, w * a.y, w * a.z, w * a.w);
 }
 
+// ---- row-subset SpMM, length-proportional pieces: a listed row of `len` edges is cut into s = max(1, ceil(len / P)) pieces of at most P edges, so a
+// 32-edge user row is one wave and the 100k-edge item is ~100 of them.  The caller's workspace (n * nsplit * d floats: nsplit = the capacity, in
+// pieces per listed row on average) holds, front to back: partial[cap][d], piece_row[cap], {P, total}, offs[n + 1].  subset_prep_kernel (ONE
+// workgroup) writes everything behind `partial` before anything reads it: it doubles P from kSubsetPieceEdges (or the caller's piece_edges) until the piece count fits `cap`
+// (a batch that lists the hub item thousands of times), scans the s values into offs and fills piece_row -- no host synchronisation.
+constexpr int kSubsetPieceEdges = 1024;         // tools/masked_rows_sweep.py at the benchmark's shapes: 128: 0.21 ms, 256: 0.17, 512: 0.16, 1024: 0.14
+constexpr int kSubsetPrepThreads = 1024;
+constexpr int kSubsetPrepRows = 8;               // listed rows per prep thread, kept in registers: lists above 8192 rows take the equal-range kernels
+constexpr int kSubsetMaxWaves = 16384;           // spmm_subset_pieces_kernel's fixed grid: its waves stride over the device-side piece count
+
+struct SubsetPlan {
+    int cap;                     // pieces the workspace holds
+    int32_t *piece_row;          // [cap] listed-row index of every piece
+    int32_t *meta;               // {P, total}
+    int32_t *offs;               // [n + 1] first piece of every listed row
+};
+
+__global__ __launch_bounds__(kSubsetPrepThreads) void subset_prep_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ rows, int n, int piece_edges,
+                                                                          SubsetPlan S) {
+    constexpr int NW = kSubsetPrepThreads / kWave, R = kSubsetPrepRows;
+    __shared__ long long wsum[NW];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid >> 6;
+    const int per = (n + kSubsetPrepThreads - 1) / kSubsetPrepThreads;    // <= R: the host sends longer lists to the equal-range kernels
+    const int lo = min(n, tid * per), hi = min(n, lo + per);              // this thread's listed rows
+    int len[R];                                                           // every row length is loaded once, all loads in flight together
+    {
+        int r[R];
+#pragma unroll
+        for (int k = 0; k < R; ++k) r[k] = lo + k < hi ? rows[lo + k] : -1;
+#pragma unroll
+        for (int k = 0; k < R; ++k) len[k] = r[k] >= 0 ? rowptr[r[k] + 1] - rowptr[r[k]] : -1;
+    }
+    auto pieces_of = [](int l, unsigned P) { return (unsigned)l > P ? ((unsigned)l + P - 1u) / P : 1u; };       // 32-bit: l < 2^31, P <= 2^31
+    unsigned P = (unsigned)piece_edges;
+    long long mine, incl, total;
+    for (;;) {
+        mine = 0;
+#pragma unroll
+        for (int k = 0; k < R; ++k) if (len[k] >= 0) mine += pieces_of(len[k], P);
+        incl = mine;                                                      // inclusive scan over the workgroup
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) { const long long o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+        __syncthreads();                                                  // wsum of the previous trip has been read
+        if (lane == kWave - 1) wsum[wv] = incl;
+        __syncthreads();
+        total = 0;
+        long long before = 0;
+#pragma unroll
+        for (int k = 0; k < NW; ++k) { const long long v = wsum[k]; total += v; if (k < wv) before += v; }
+        incl += before;
+        if (total <= S.cap) break;                                        // P >= the longest row (2^31 at the latest) gives total = n <= cap
+        P *= 2;
+    }
+    // offsets, and the piece -> row map; a row with more than one piece is written by its whole wave, 64 pieces at a time (a hub row has hundreds)
+    int first = (int)(incl - mine);
+#pragma unroll
+    for (int k = 0; k < R; ++k) {                                         // uniform trip count: the ballot below needs every lane
+        const int t = lo + k;
+        const int sp = len[k] >= 0 ? (int)pieces_of(len[k], P) : 0;
+        if (sp > 0) S.offs[t] = first;
+        if (sp == 1) S.piece_row[first] = t;
+        for (unsigned long long many = __ballot(sp > 1); many; many &= many - 1ull) {
+            const int l = __builtin_ctzll(many);
+            const int sp_l = __builtin_amdgcn_readlane(sp, l), first_l = __builtin_amdgcn_readlane(first, l), t_l = __builtin_amdgcn_readlane(t, l);
+            for (int i = lane; i < sp_l; i += kWave) S.piece_row[first_l + i] = t_l;
+        }
+        first += sp;
+    }
+    if (tid == 0) { S.meta[0] = (int)min(P, 0x7fffffffu); S.meta[1] = (int)total; S.offs[n] = (int)total; }
+}
+
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void spmm_subset_pieces_kernel(CsrDev A, const float *__restrict__ X, int d, const int32_t *__restrict__ rows, SubsetPlan S,
+                                                                     float *__restrict__ partial) {
+    const int lane = threadIdx.x & (kWave - 1), q = lane % LPR;
+    const int total = S.meta[1], n_waves = gridDim.x * kWavesPerBlock;
+    for (int piece = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); piece < total; piece += n_waves) {
+        const int t = S.piece_row[piece];
+        const int k = piece - S.offs[t], sp = S.offs[t + 1] - S.offs[t];
+        const int r = rows[t];
+        const int begin = A.rowptr[r], end = A.rowptr[r + 1];
+        const int per = (end - begin + sp - 1) / sp;                      // <= P; (sp - 1) * per < end - begin
+        const int b = begin + k * per, e = min(end, b + per);
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (b < e) a = spmm_gather<LPR, 4>(A.col, A.val, b, e, X, d, lane);
+        a = group_reduce<LPR>(a);
+        if (lane < LPR && q * 4 < d) *reinterpret_cast<float4 *>(partial + (size_t)piece * d + q * 4) = a;
+    }
+}
+
+// out_c[t] = w * (sum_k layer_k[r] + the row's pieces).  One wave per listed row: lane group g of the G = 64 / LPR adds pieces g, g + G, ... in that order,
+// eight loads in flight (the hub item has hundreds of pieces), group 0 also the layer rows; the groups are then added in a fixed tree.  The order
+// depends on the row's piece count only.
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void subset_pieces_finish_kernel(const float *__restrict__ partial, int n, SubsetPlan S, int d, const int32_t *__restrict__ rows,
+                                                                       LayerPtrs L, float alpha, float *__restrict__ out_c, const float *__restrict__ row_weight) {
+    constexpr int G = kWave / LPR;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int g = lane / LPR, q = lane % LPR;
+    const int t = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (t >= n) return;
+    const bool qact = q * 4 < d;
+    const int r = rows[t];
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g == 0 && qact)
+        for (int k = 0; k < L.n; ++k) a = add4(a, *reinterpret_cast<const float4 *>(L.p[k] + (size_t)r * d + q * 4));
+    const int p1 = S.offs[t + 1];
+    if (qact)
+        for (int p = S.offs[t] + g; p < p1; p += 8 * G) {
+            float4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (p + u * G < p1) v[u] = *reinterpret_cast<const float4 *>(partial + (size_t)(p + u * G) * d + q * 4);
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (p + u * G < p1) a = add4(a, v[u]);
+        }
+    a = group_reduce<LPR>(a);
+    if (lane >= LPR || !qact) return;
+    const float w = row_weight ? alpha * row_weight[t] : alpha;
+    *reinterpret_cast<float4 *>(out_c + (size_t)t * d + q * 4) = make_float4(w * a.x, w * a.y, w * a.z, w * a.w);
+}
+
+// Where the plan lives in a workspace of n * nsplit * d floats; cap < n (nsplit = 1, or a handful of narrow rows): no room, fixed-split kernels.
+// So does a list longer than the one-workgroup prep kernel holds in registers (the step lists 3B rows).
+static bool subset_plan(void *workspace, long long n, long long nsplit, long long d, SubsetPlan *S) {
+    const long long words = n * nsplit * d, tail = n + 3;
+    const long long cap = (words - tail) / (d + 1);
+    if (cap < n || cap > 0x7fffffffll || n > (long long)kSubsetPrepThreads * kSubsetPrepRows) return false;
+    int32_t *w = (int32_t *)workspace;
+    S->cap = (int)cap;
+    S->piece_row = w + cap * d;
+    S->meta = S->piece_row + cap;
+    S->offs = S->meta + 2;
+    return true;
+}
+
 // out = alpha * sum_k layers[k]  (element-wise over up to 8 equally shaped tables; the LightGCN mean over layers, LightGCN.py:236-240,
 // in ONE pass instead of a clone + L adds + a division)
 __global__ __launch_bounds__(kBlock) void tables_sum_kernel(LayerPtrs L, long long n4, float alpha, float4 *__restrict__ out) {
@@ -715,6 +852,7 @@ struct BlockedDev {
     const int32_t *rec_col;       // col | slot << 24
     const float *rec_val;
     float *partial;               // [n_pieces][d] raw sums of split-row pieces (wave_rows entry -(2 + t))
+    const uint32_t *xbits;        // MASKED only: one bit per operand row; X is zero on the rows whose bit is clear
 };
 
 // spmm_epilogue for CPL adjacent columns per lane (d = 64 * CPL); same arithmetic (a wave writes one 256-B / 512-B row at a time)
@@ -745,7 +883,13 @@ __device__ __forceinline__ void spmm_epilogue1(const Epi &ep, int row, int lane,
     }
 }
 
-template <int RPW, int MODE, int UNR, int CPL, int LD = 64 * CPL>       // LD: row stride (floats) of the operand and of every table the epilogue touches
+// MASKED (the first backward hop: X = the batch gradient, non-zero on <= 3B rows whose bits are set in P.xbits): every lane tests the bit of
+// its own record's column, one ballot gives the batch's hits, and only those are gathered -- kMaskedUnr loads first, then their FMAs, in
+// record order.  A skipped record would have added fmaf(v, 0, acc) = acc (accumulators start at +0 and a sum of products never rounds to
+// -0), so the result has the bits of the unmasked kernel on the same operand; an all-clear batch costs its record load and the ballot.
+constexpr int kMaskedUnr = 8;
+
+template <int RPW, int MODE, int UNR, int CPL, int LD = 64 * CPL, bool MASKED = false>       // LD: row stride (floats) of the operand and of every table the epilogue touches
 __global__ __launch_bounds__(kBlock) void spmm_blocked64_kernel(BlockedDev P, const float *__restrict__ X, Epi ep) {
     static_assert(RPW == 16 || RPW == 32, "accumulators are 32-register vectors");
     static_assert(CPL == 1 || CPL == 2, "d = 64 (one column per lane) or d = 128 (two adjacent columns per lane)");
@@ -759,6 +903,41 @@ __global__ __launch_bounds__(kBlock) void spmm_blocked64_kernel(BlockedDev P, co
         for (int r = 0; r < 32; ++r) acc[c][r] = 0.f;
     const int begin = P.wave_ptr[w], end = P.wave_ptr[w + 1];
     const float *xl = X + lane * CPL;
+    if (MASKED) {
+        // three stages in flight per wave: the records of batch b + 2, the bitmap words of batch b + 1, the gathers of batch b
+        int c0 = 0, c1 = 0; unsigned w0 = 0;
+        if (begin < end) c0 = __builtin_nontemporal_load(P.rec_col + begin + lane);
+        if (begin + 64 < end) c1 = __builtin_nontemporal_load(P.rec_col + begin + 64 + lane);
+        if (begin < end) w0 = P.xbits[((unsigned)c0 & 0xffffffu) >> 5];
+        for (int base = begin; base < end; base += 64) {
+            const int c_cur = c0; const unsigned w_cur = w0;
+            c0 = c1;
+            if (base + 128 < end) c1 = __builtin_nontemporal_load(P.rec_col + base + 128 + lane);
+            if (base + 64 < end) w0 = P.xbits[((unsigned)c0 & 0xffffffu) >> 5];
+            unsigned long long hits = __ballot((w_cur >> (c_cur & 31)) & 1u);
+            while (hits) {
+                float x[kMaskedUnr][CPL], vs[kMaskedUnr]; int cs[kMaskedUnr], js[kMaskedUnr];
+#pragma unroll
+                for (int t = 0; t < kMaskedUnr; ++t) {           // wave-uniform: the ballot, the bit scan and the readlane index are scalar
+                    js[t] = hits ? __builtin_ctzll(hits) : -1;
+                    hits &= hits - 1ull;
+                    if (js[t] < 0) continue;
+                    cs[t] = __builtin_amdgcn_readlane(c_cur, js[t]);
+                    vs[t] = P.rec_val[base + js[t]];             // per hit, a uniform load beside the gather: half the record stream (per batch measured 0.34 against 0.32 ms)
+                    const float *src = xl + (size_t)(cs[t] & 0xffffff) * LD;
+                    if (CPL == 2) { const float2 v2 = *reinterpret_cast<const float2 *>(src); x[t][0] = v2.x; x[t][CPL - 1] = v2.y; }
+                    else x[t][0] = src[0];
+                }
+#pragma unroll
+                for (int t = 0; t < kMaskedUnr; ++t) {
+                    if (js[t] < 0) continue;
+                    const int slot = ((unsigned)cs[t] >> 24) & 31;
+#pragma unroll
+                    for (int c = 0; c < CPL; ++c) acc[c][slot] = fmaf(vs[t], x[t][c], acc[c][slot]);
+                }
+            }
+        }
+    } else {
     int rc = 0; float rv = 0.f;
     if (begin < end) { rc = __builtin_nontemporal_load(P.rec_col + begin + lane); if (!ARL_SPMM_EXP_NOVAL) rv = __builtin_nontemporal_load(P.rec_val + begin + lane); }
     for (int base = begin; base < end; base += 64) {
@@ -788,6 +967,7 @@ __global__ __launch_bounds__(kBlock) void spmm_blocked64_kernel(BlockedDev P, co
             }
         }
     }
+    }
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
         const int row = P.wave_rows[w * RPW + r];
@@ -806,8 +986,19 @@ __global__ __launch_bounds__(kBlock) void spmm_blocked64_kernel(BlockedDev P, co
 #ifndef ARL_D128_HALF_HOPS
 #define ARL_D128_HALF_HOPS 1
 #endif
+// one launch of the blocked kernel; `xbits` selects the MASKED instantiation (AXPBY epilogue only)
+template <int RPW, int MODE, int UNR, int CPL, int LD>
+static int launch_blocked64(dim3 grid, dim3 block, hipStream_t st, const BlockedDev &D, const float *X, const Epi &ep) {
+    if (D.xbits) {
+        if constexpr (MODE == EPI_AXPBY) hipLaunchKernelGGL((spmm_blocked64_kernel<RPW, MODE, UNR, CPL, LD, true>), grid, block, 0, st, D, X, ep);
+        else return ARL_E_ARG;
+    } else hipLaunchKernelGGL((spmm_blocked64_kernel<RPW, MODE, UNR, CPL, LD, false>), grid, block, 0, st, D, X, ep);
+    ARL_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
 template <int MODE>
-int launch_spmm_blocked(const arl_blocked *P, const float *X, int64_t d, const Epi &ep, hipStream_t st) {
+int launch_spmm_blocked(const arl_blocked *P, const float *X, int64_t d, const Epi &ep, hipStream_t st, const uint32_t *xbits = nullptr) {
     if (!P || !X) return ARL_E_NULL;
     if (d != 64 && d != 128) return ARL_E_DIM;
     if (P->n_waves < 0 || P->n_waves > 0x7fffffffll / 64) return ARL_E_RANGE;
@@ -816,11 +1007,12 @@ int launch_spmm_blocked(const arl_blocked *P, const float *X, int64_t d, const E
     if (!P->wave_ptr || !P->wave_rows || !P->rec_col || !P->rec_val) return ARL_E_NULL;
     if (P->n_split < 0 || P->n_split > 0x7fffffffll) return ARL_E_RANGE;
     if (P->n_split > 0 && (!P->split_row || !P->split_first || !P->split_count || !P->partial)) return ARL_E_NULL;
-    BlockedDev D = {(int)P->n_waves, P->wave_ptr, P->wave_rows, P->rec_col, P->rec_val, P->partial};
+    BlockedDev D = {(int)P->n_waves, P->wave_ptr, P->wave_rows, P->rec_col, P->rec_val, P->partial, xbits};
     const int64_t wpg = P->waves_per_group ? P->waves_per_group : kWavesPerBlock;
     if (wpg != 1 && wpg != 2 && wpg != 4) return ARL_E_ARG;
     const dim3 grid((unsigned)((P->n_waves + wpg - 1) / wpg)), block((unsigned)(wpg * kWave));
     if (P->loads_in_flight != 16 && P->loads_in_flight != 32) return ARL_E_ARG;
+    int rc;
 #if ARL_D128_HALF_HOPS
     if (d == 128) {
         // d = 128 as two d = 64 passes over the column halves of the 128-wide tables (row stride 128): the one-column-per-lane kernel moves
@@ -838,10 +1030,10 @@ int launch_spmm_blocked(const arl_blocked *P, const float *X, int64_t d, const E
             if (e2.P) e2.P += off;
             if (e2.M) e2.M += off;
             if (e2.V) e2.V += off;
-            if (P->rows_per_wave == 16) hipLaunchKernelGGL((spmm_blocked64_kernel<16, MODE, 16, 1, 128>), grid, block, 0, st, D, X + off, e2);
-            else if (P->loads_in_flight == 16) hipLaunchKernelGGL((spmm_blocked64_kernel<32, MODE, 16, 1, 128>), grid, block, 0, st, D, X + off, e2);
-            else hipLaunchKernelGGL((spmm_blocked64_kernel<32, MODE, 32, 1, 128>), grid, block, 0, st, D, X + off, e2);
-            ARL_LAUNCH_CHECK();
+            if (P->rows_per_wave == 16) rc = launch_blocked64<16, MODE, 16, 1, 128>(grid, block, st, D, X + off, e2);
+            else if (P->loads_in_flight == 16) rc = launch_blocked64<32, MODE, 16, 1, 128>(grid, block, st, D, X + off, e2);
+            else rc = launch_blocked64<32, MODE, 32, 1, 128>(grid, block, st, D, X + off, e2);
+            if (rc != ARL_OK) return rc;
             if (P->n_split > 0) {
                 CsrDev C = {};
                 C.n_long = (int)P->n_split; C.long_row = P->split_row; C.long_first = P->split_first; C.long_count = P->split_count; C.partial = P->partial;
@@ -854,12 +1046,12 @@ int launch_spmm_blocked(const arl_blocked *P, const float *X, int64_t d, const E
     }
 #endif
     if (d == 128) {                                      // two columns per lane: 64 accumulator registers, 16 rows in flight
-        if (P->rows_per_wave == 16) hipLaunchKernelGGL((spmm_blocked64_kernel<16, MODE, 16, 2>), grid, block, 0, st, D, X, ep);
-        else hipLaunchKernelGGL((spmm_blocked64_kernel<32, MODE, 16, 2>), grid, block, 0, st, D, X, ep);
-    } else if (P->rows_per_wave == 16) hipLaunchKernelGGL((spmm_blocked64_kernel<16, MODE, 16, 1>), grid, block, 0, st, D, X, ep);
-    else if (P->loads_in_flight == 16) hipLaunchKernelGGL((spmm_blocked64_kernel<32, MODE, 16, 1>), grid, block, 0, st, D, X, ep);
-    else hipLaunchKernelGGL((spmm_blocked64_kernel<32, MODE, 32, 1>), grid, block, 0, st, D, X, ep);
-    ARL_LAUNCH_CHECK();
+        if (P->rows_per_wave == 16) rc = launch_blocked64<16, MODE, 16, 2, 128>(grid, block, st, D, X, ep);
+        else rc = launch_blocked64<32, MODE, 16, 2, 128>(grid, block, st, D, X, ep);
+    } else if (P->rows_per_wave == 16) rc = launch_blocked64<16, MODE, 16, 1, 64>(grid, block, st, D, X, ep);
+    else if (P->loads_in_flight == 16) rc = launch_blocked64<32, MODE, 16, 1, 64>(grid, block, st, D, X, ep);
+    else rc = launch_blocked64<32, MODE, 32, 1, 64>(grid, block, st, D, X, ep);
+    if (rc != ARL_OK) return rc;
     if (P->n_split > 0) {                                // split rows: add the pieces in piece order and run the epilogue
         CsrDev C = {};
         C.n_long = (int)P->n_split; C.long_row = P->split_row; C.long_first = P->split_first; C.long_count = P->split_count; C.partial = P->partial;
@@ -4623,6 +4815,16 @@ int arl_spmm_blocked_f32(const arl_blocked *P, const float *X, int64_t d, float 
     return launch_spmm_blocked<EPI_AXPBY>(P, X, d, ep, (hipStream_t)stream);
 }
 
+int arl_spmm_blocked_flagged_f32(const arl_blocked *P, const float *X, int64_t d, const uint32_t *xbits, float alpha, float beta, const float *Z,
+                                 const uint8_t *zflags, float *Y, arl_stream_t stream) {
+    if (!Y || !xbits) return ARL_E_NULL;
+    if (beta != 0.f && !Z) return ARL_E_NULL;
+    if (Y == X) return ARL_E_ARG;
+    Epi ep = {};
+    ep.alpha = alpha; ep.beta = beta; ep.Z = (beta != 0.f) ? Z : nullptr; ep.zflags = zflags; ep.Y = Y;
+    return launch_spmm_blocked<EPI_AXPBY>(P, X, d, ep, (hipStream_t)stream, xbits);
+}
+
 int arl_spmm_blocked_rscale_f32(const arl_blocked *P, const float *X, int64_t d, const float *row_scale, float alpha, float beta, const float *Z,
                                 float *Y, arl_stream_t stream) {
     if (!Y || !row_scale) return ARL_E_NULL;
@@ -4708,9 +4910,16 @@ int64_t arl_spmm_csr_rows_workspace_bytes(int64_t n_rows_sel, int64_t nsplit, in
     return (n_rows_sel < 0 || nsplit < 1 || d < 0) ? 0 : (int64_t)sizeof(float) * n_rows_sel * nsplit * d;
 }
 
-int arl_spmm_csr_rows_f32(const arl_csr *A, const float *X, int64_t d, const int32_t *rows, int64_t n_rows_sel, int64_t nsplit,
-                          const float *const *layers, int64_t n_layers, float alpha, const float *row_weight, float *out_c, void *workspace,
-                          arl_stream_t stream) {
+int64_t arl_spmm_csr_rows_scratch_offset(int64_t n_rows_sel, int64_t nsplit, int64_t d) {
+    SubsetPlan S = {};
+    if (n_rows_sel <= 0 || nsplit < 1 || nsplit > 1024 || d <= 0 || d > 256 || (d & 3) || !subset_plan(nullptr, n_rows_sel, nsplit, d, &S)) return -1;
+    return (int64_t)S.cap * (d + 1);        // word index of {P, total}; offs follow, piece_row[cap] lies just before
+}
+
+int arl_spmm_csr_rows_pieces_f32(const arl_csr *A, const float *X, int64_t d, const int32_t *rows, int64_t n_rows_sel, int64_t nsplit, int64_t piece_edges,
+                                 const float *const *layers, int64_t n_layers, float alpha, const float *row_weight, float *out_c, void *workspace,
+                                 arl_stream_t stream) {
+    if (piece_edges < 0 || piece_edges > 0x40000000ll) return ARL_E_RANGE;
     if (!A || !X || !rows || !out_c || !workspace || !A->rowptr) return ARL_E_NULL;
     if (A->nnz > 0 && (!A->col || !A->val)) return ARL_E_NULL;
     if (n_layers < 0 || n_layers > 8 || (n_layers > 0 && !layers)) return ARL_E_ARG;
@@ -4727,8 +4936,22 @@ int arl_spmm_csr_rows_f32(const arl_csr *A, const float *X, int64_t d, const int
     const unsigned grid = (unsigned)((tasks + kWavesPerBlock - 1) / kWavesPerBlock);
     const int di = (int)d, n = (int)n_rows_sel, ns = (int)nsplit;
     float *part = (float *)workspace;
+    SubsetPlan S = {};
+    const bool pieces = subset_plan(workspace, n_rows_sel, nsplit, d, &S);
+    if (pieces) {
+        hipLaunchKernelGGL(subset_prep_kernel, dim3(1), dim3(kSubsetPrepThreads), 0, st, A->rowptr, rows, n, piece_edges > 0 ? (int)piece_edges : kSubsetPieceEdges, S);
+        ARL_LAUNCH_CHECK();
+    }
+    const unsigned grid_p = (unsigned)(((S.cap < kSubsetMaxWaves ? S.cap : kSubsetMaxWaves) + kWavesPerBlock - 1) / kWavesPerBlock);
 #define ARL_SUBSET_CASE(LPRV)                                                                                                  \
     do {                                                                                                                       \
+        if (pieces) {                                                                                                          \
+            hipLaunchKernelGGL((spmm_subset_pieces_kernel<LPRV>), dim3(grid_p), dim3(kBlock), 0, st, D, X, di, rows, S, part); \
+            ARL_LAUNCH_CHECK();                                                                                                \
+            hipLaunchKernelGGL((subset_pieces_finish_kernel<LPRV>), dim3((unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, st, part, n, S, di, rows, LP, alpha, out_c, row_weight); \
+            ARL_LAUNCH_CHECK();                                                                                                \
+            break;                                                                                                             \
+        }                                                                                                                      \
         hipLaunchKernelGGL((spmm_subset_kernel<LPRV>), dim3(grid), dim3(kBlock), 0, st, D, X, di, rows, n, ns, part);          \
         ARL_LAUNCH_CHECK();                                                                                                    \
         const unsigned g2 = (unsigned)((n + kWavesPerBlock * (kWave / LPRV) - 1) / (kWavesPerBlock * (kWave / LPRV)));         \
@@ -4742,6 +4965,12 @@ int arl_spmm_csr_rows_f32(const arl_csr *A, const float *X, int64_t d, const int
     else ARL_SUBSET_CASE(64);
 #undef ARL_SUBSET_CASE
     return ARL_OK;
+}
+
+int arl_spmm_csr_rows_f32(const arl_csr *A, const float *X, int64_t d, const int32_t *rows, int64_t n_rows_sel, int64_t nsplit,
+                          const float *const *layers, int64_t n_layers, float alpha, const float *row_weight, float *out_c, void *workspace,
+                          arl_stream_t stream) {
+    return arl_spmm_csr_rows_pieces_f32(A, X, d, rows, n_rows_sel, nsplit, 0, layers, n_layers, alpha, row_weight, out_c, workspace, stream);
 }
 
 int arl_mark_rows_u8(uint8_t *flags, const int32_t *idx, int64_t n, int32_t value, arl_stream_t stream) {

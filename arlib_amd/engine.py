@@ -81,7 +81,7 @@ class PropagationEngine:
         # state that later steps fill in (nothing below allocates device memory here)
         self._G_dirty = True                        # the sparse steps keep G all-zero between calls; dense users leave it dirty
         self._noise_seed, self._noise_stream = None, 0      # in-kernel noise (SimGCL family) / dropout masks (SSL4Rec): see _streams()
-        self.nsplit = 32            # edge ranges per batch row in the row-subset hop (cfg2 sweep: 8: 0.56 ms, 16: 0.33, 32/64: 0.21, 128: 0.36)
+        self.nsplit = 32            # capacity of the row-subset hop's workspace, in pieces per batch row on average (rows are cut by length: ops.spmm_rows; cfg2 needs ~1.3)
         self.flags = self.bits = self.dup_bits = self.hops = None                                   # node-sized, _sparse_buffers()
         self._sparse_B, self._sb_cache = None, {}
         self.Gc = self.out_c = self.rows_ws = self.ar = self.arB = self._ws = None                 # batch-sized, _sparse_buffers()

@@ -735,8 +735,9 @@ def spmm_flagged(A, X, xflags=None, alpha=1.0, beta=0.0, Z=None, zflags=None, ou
     L, zp, st = _lib.lib(), (_ptr(Z) if beta != 0.0 else None), _stream()
     tok = EVENT_HOOK.begin('masked' if xflags is not None else 'axpby') if EVENT_HOOK is not None else None
     csr = lambda p: check(L.arl_spmm_csr_flagged_f32(p, _ptr(X), d, _ptr(xflags), alpha, beta, zp, _ptr(zflags), _ptr(Y), st), 'arl_spmm_csr_flagged_f32')
-    if xflags is not None:              # the masked hop skips most edges: row-per-group kernel
-        csr(C.byref(A._struct(d)))
+    if xflags is not None:              # the masked hop skips most edges: the blocked record stream with a bit test per record, else the row-per-group kernel
+        _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_flagged_f32(p, _ptr(X), d, _ptr(xflags), alpha, beta, zp, _ptr(zflags), _ptr(Y), st),
+                                             'arl_spmm_blocked_flagged_f32'), csr)
     else:
         _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(zflags), _ptr(Y), st), 'arl_spmm_blocked_f32'), csr)
     if tok is not None:
@@ -744,11 +745,24 @@ def spmm_flagged(A, X, xflags=None, alpha=1.0, beta=0.0, Z=None, zflags=None, ou
     return Y
 
 
-ROWS_NSPLIT = 16     # default number of edge ranges per listed row of the row-subset hop
+ROWS_NSPLIT = 16     # default capacity of the row-subset hop's workspace, in pieces per listed row on average
 
 
-def spmm_rows(A, X, rows, layers=(), alpha=1.0, nsplit=ROWS_NSPLIT, out=None, workspace=None, check_range=True, row_weight=None):
-    """out[t] = alpha * ( sum_k layers[k][rows[t]] + (A @ X)[rows[t]] ) for the listed rows only (duplicates allowed)."""
+def spmm_rows_plan(left_in, n, nsplit, d):
+    """What the last spmm_rows call with these sizes left in its workspace `left_in`: (piece_edges, n_pieces, offsets [n + 1] int32 view), or None when the
+    call took the equal-range form (nsplit = 1, or no room for the piece tables).  Reads the device: tests and tools only."""
+    off = _lib.lib().arl_spmm_csr_rows_scratch_offset(n, nsplit, d)
+    if off < 0:
+        return None
+    w = left_in.view(torch.int32)
+    meta = w[off:off + 2].tolist()
+    return meta[0], meta[1], w[off + 2:off + 3 + n]
+
+
+def spmm_rows(A, X, rows, layers=(), alpha=1.0, nsplit=ROWS_NSPLIT, out=None, workspace=None, check_range=True, row_weight=None, piece_edges=0):
+    """out[t] = alpha * ( sum_k layers[k][rows[t]] + (A @ X)[rows[t]] ) for the listed rows only (duplicates allowed).
+    A row is cut into pieces of at most `piece_edges` edges (0 = the library's default), doubled on the device until the pieces fit the
+    workspace of n * nsplit * d floats; the result is a deterministic function of (graph, rows, nsplit, piece_edges)."""
     d = _check_xy(A, X, 'X', A.n_cols)
     _dev(rows, torch.int32, 'rows', 1)
     n = rows.numel()
@@ -772,8 +786,12 @@ def spmm_rows(A, X, rows, layers=(), alpha=1.0, nsplit=ROWS_NSPLIT, out=None, wo
     tok = EVENT_HOOK.begin('rows') if EVENT_HOOK is not None else None
     if row_weight is not None and (_dev(row_weight, torch.float32, 'row_weight', 1).numel() != n):
         raise ValueError('spmm_rows: row_weight must have one entry per listed row')
-    check(_lib.lib().arl_spmm_csr_rows_f32(C.byref(s), _ptr(X), d, _ptr(rows), n, nsplit, C.cast(arr, C.c_void_p), len(layers), alpha, _ptr(row_weight),
-                                           _ptr(out), _ptr(workspace), _stream()), 'arl_spmm_csr_rows_f32')
+    if piece_edges:
+        check(_lib.lib().arl_spmm_csr_rows_pieces_f32(C.byref(s), _ptr(X), d, _ptr(rows), n, nsplit, int(piece_edges), C.cast(arr, C.c_void_p), len(layers), alpha,
+                                                      _ptr(row_weight), _ptr(out), _ptr(workspace), _stream()), 'arl_spmm_csr_rows_pieces_f32')
+    else:
+        check(_lib.lib().arl_spmm_csr_rows_f32(C.byref(s), _ptr(X), d, _ptr(rows), n, nsplit, C.cast(arr, C.c_void_p), len(layers), alpha, _ptr(row_weight),
+                                               _ptr(out), _ptr(workspace), _stream()), 'arl_spmm_csr_rows_f32')
     if tok is not None:
         EVENT_HOOK.end(tok)
     return out

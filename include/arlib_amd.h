@@ -125,10 +125,18 @@ int arl_spmm_csr_adam_f32(const arl_csr *A, const float *X, int64_t d, float alp
  *                             (uint32 words, bit c&31 of word c>>5; NULL = dense gather) and Z is read only where
  *                             zflags != 0 (NULL = everywhere).  xbits: ceil(n_cols/32) words, zflags: [n_rows] bytes.
  *   arl_spmm_csr_rows_f32     out_c[t] = alpha * w[t] * ( sum_k layers[k][rows[t]] + (A X)[rows[t]] ), t < n_rows_sel: only the
- *                             listed rows are produced (duplicates allowed).  Each row is cut into `nsplit` edge ranges;
- *                             workspace = arl_spmm_csr_rows_workspace_bytes(n_rows_sel, nsplit, d).  layers: HOST array of
+ *                             listed rows are produced (duplicates allowed).  A row of len edges is cut into max(1, ceil(len / P))
+ *                             pieces, P = 1024 edges, doubled on the device until all pieces fit the workspace: `nsplit` is its
+ *                             capacity in pieces per listed row on average, workspace =
+ *                             arl_spmm_csr_rows_workspace_bytes(n_rows_sel, nsplit, d) (nsplit = 1, a workspace too small for
+ *                             the piece tables, or more than 8192 listed rows -- the piece tables are built by one workgroup --:
+ *                             every row cut into nsplit equal ranges).  The result is a deterministic function
+ *                             of (graph, rows, nsplit).  layers: HOST array of
  *                             n_layers (<= 8) device pointers to [n_rows, d] tables.  row_weight: optional [n_rows_sel] factors
  *                             w (NULL = 1; the user-sharded step passes 1 for samples whose user the rank owns, 0 otherwise).
+ *   arl_spmm_csr_rows_pieces_f32   the same with the starting P given (piece_edges; 0 = the default): tuning sweeps.
+ *   arl_spmm_csr_rows_scratch_offset   index (in 32-bit words) of the pair {P used, piece count} that the call leaves in the
+ *                             workspace, followed by the n_rows_sel + 1 piece offsets of the listed rows; -1 = equal-range form.
  *   arl_spmm_csr_adam_f32's zflags has the same meaning (NULL = read Z everywhere).
  *   arl_mark_rows_u8 / arl_zero_rows_f32: flags[idx[t]] = value / dst[idx[t], :] = 0 -- set and clear the batch's sparse state. */
 int arl_spmm_csr_flagged_f32(const arl_csr *A, const float *X, int64_t d, const uint32_t *xbits, float alpha, float beta,
@@ -137,6 +145,10 @@ int64_t arl_spmm_csr_rows_workspace_bytes(int64_t n_rows_sel, int64_t nsplit, in
 int arl_spmm_csr_rows_f32(const arl_csr *A, const float *X, int64_t d, const int32_t *rows, int64_t n_rows_sel,
                           int64_t nsplit, const float *const *layers, int64_t n_layers, float alpha, const float *row_weight,
                           float *out_c, void *workspace, arl_stream_t stream);
+int arl_spmm_csr_rows_pieces_f32(const arl_csr *A, const float *X, int64_t d, const int32_t *rows, int64_t n_rows_sel,
+                                 int64_t nsplit, int64_t piece_edges, const float *const *layers, int64_t n_layers, float alpha,
+                                 const float *row_weight, float *out_c, void *workspace, arl_stream_t stream);
+int64_t arl_spmm_csr_rows_scratch_offset(int64_t n_rows_sel, int64_t nsplit, int64_t d);
 int arl_mark_rows_u8(uint8_t *flags, const int32_t *idx, int64_t n, int32_t value, arl_stream_t stream);
 /* set (set != 0) or clear the bits idx[t] of a bitmap with atomic OR / AND (duplicates allowed) */
 int arl_mark_rows_bits_u32(uint32_t *bits, const int32_t *idx, int64_t n, int32_t set, arl_stream_t stream);
@@ -183,6 +195,11 @@ typedef struct arl_blocked {
 } arl_blocked;
 int arl_spmm_blocked_f32(const arl_blocked *P, const float *X, int64_t d, float alpha, float beta, const float *Z,
                          const uint8_t *zflags, float *Y, arl_stream_t stream);
+/* The flag-masked hop (arl_spmm_csr_flagged_f32) on the blocked plan: X is zero except on rows whose bit is set in xbits (required).  Each
+ * lane tests the bit of its own record, a ballot gives the 64-record batch's hits and only those are gathered, in record order, so the result
+ * has the bits of arl_spmm_blocked_f32 on the same operand.  The plan's hub rows stay with arl_spmm_csr_flagged_f32. */
+int arl_spmm_blocked_flagged_f32(const arl_blocked *P, const float *X, int64_t d, const uint32_t *xbits, float alpha, float beta,
+                                 const float *Z, const uint8_t *zflags, float *Y, arl_stream_t stream);
 /* Y = alpha * diag(row_scale) (A X) + beta * Z: the product with a diagonal factor in the epilogue (PGA applies D^-1/2 W D^-1/2 in
  * factors and keeps W's values fixed); CSR and blocked schedules. */
 int arl_spmm_csr_rscale_f32(const arl_csr *A, const float *X, int64_t d, const float *row_scale, float alpha, float beta,
