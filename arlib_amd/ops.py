@@ -6,8 +6,6 @@ the whole GPU host), then passes raw pointers + sizes + the current HIP stream t
 No op has a CPU fallback.
 """
 import ctypes as C
-import os
-import time
 import numpy as np
 import torch
 
@@ -1330,7 +1328,7 @@ def cw_topk_term(X, n_user_rows, n_real, top_idx, targets, c=None, want_w=True, 
     return loss, G, w
 
 
-TOPK_FORM2 = os.environ.get('ARL_TOPK_FORM2', '1') != '0'      # (A/B: ARL_TOPK_FORM2=0 keeps the first form of score_mask_topk's fp16 stream)
+TOPK_FORM2 = True         # the second form of score_mask_topk's fp16 stream at d = 64; tests and probes set it to False for a pass to obtain the first (reference) form
 TOPK_STATS = {'calls': 0, 'warm': 0, 'cold_repeats': 0}     # counters for benches: warm-started calls and how many of them had to be repeated cold
 
 
@@ -1436,27 +1434,22 @@ def score_mask_topk(Pu, Pi, k, mask_rowptr=None, mask_col=None, exact=False, war
                     order = ent[0]; ent[1] += 1
         elif item_order is not None:
             raise ValueError("score_mask_topk: item_order must be 'norm', None or an int32 permutation")
-    timed = os.environ.get('ARL_TOPK_TIME') == '1'          # diagnostics: wall time of the pass itself, between device synchronisations
     evs = None
-    if TOPK_STATS.get('record_events') or os.environ.get('ARL_TOPK_TIME') == '2':       # diagnostics: device-side span (events on the launch stream, no host synchronisation)
+    if TOPK_STATS.get('record_events'):       # diagnostics: device-side span (events on the launch stream, no host synchronisation)
         evs = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         evs[0].record()
-    if timed:
-        torch.cuda.synchronize(); t0 = time.perf_counter()
     mode, probe = 0, None
     if ws is not None and order is not None:               # the early exit needs the norm-ordered stream
         soff = _lib.lib().arl_score_mask_topk_stats_offset(I, d)
         nst = (I + (64 if d <= 64 else 32) - 1) // (64 if d <= 64 else 32)
         mode, probe = _exit_mode((U, I, d, k, mask_rowptr is not None), ws, soff, nst, Pu.device)
     uws = None
-    if ws is not None and TOPK_FORM2 and (d == 64 or (d == 128 and os.environ.get('ARL_TOPK_FORM2_D128') == '1')):      # (d = 128: developer builds with -DARL_TOPK2_D128=1 only)           # the second form of the stream (32 users per wave, lists kept in the outputs): needs the user workspace
+    if ws is not None and TOPK_FORM2 and d == 64:          # the second form of the stream (32 users per wave, lists kept in the outputs): needs the user workspace
         uws = torch.empty(_lib.lib().arl_score_mask_topk_user_workspace_bytes(U, d), dtype=torch.uint8, device=Pu.device)
     check(_lib.lib().arl_score_mask_topk_f32(_ptr(Pu), _ptr(Pi), U, I, d, _ptr(mask_rowptr), _ptr(mask_col), k, _ptr(idx), _ptr(val), _ptr(ws),
                                              _ptr(warm_idx), _ptr(flag), _ptr(order), mode, _ptr(uws), _stream()), 'arl_score_mask_topk_f32')
     if mode == 1:
         _exit_probe_record(probe, ws, soff, nst)
-    if timed:
-        torch.cuda.synchronize(); TOPK_STATS.setdefault('ms', []).append(1e3 * (time.perf_counter() - t0))
     if evs is not None:
         evs[1].record(); TOPK_STATS.setdefault('events', []).append(evs)
     TOPK_STATS['calls'] += 1

@@ -1,6 +1,6 @@
 """Per-wave section timers of score_mask_topk's second form (topk2_main_kernel), in clock ticks of s_memtime, averaged over workgroups.
-Needs the instrumented build:  make -C arlib_amd/csrc variant NAME=t2prof DEFS=-DARL_TOPK2_PROF
-    ARLIB_AMD_LIB=arlib_amd/lib/libarlib_amd_t2prof.so python3 tools/topk2_prof.py      (the timers overwrite top_val: never the product)"""
+Needs the instrumented build:  make -C arlib_amd/csrc prof
+    ARLIB_AMD_LIB=arlib_amd/lib/libarlib_amd_prof.so python3 tools/topk2_prof.py      (the timers overwrite top_val: never the product)"""
 import sys, os, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,5 +1,5 @@
 """score_mask_topk at cfg2 size (1 M x 100 K, d = 64, k = 50) on tables with and without norm structure: time per pass (cold and warm-started) and
-the share of the item stream the exact early exit skipped.  A/B builds: ARLIB_AMD_LIB=<variant .so> (make variant ...).
+the share of the item stream the exact early exit skipped.
   random      -- i.i.d. normal tables: item norms within a few percent of each other, nothing to skip
   propagated  -- xavier tables after ONE normalised-adjacency hop on the SYN-v1 graph (what an attack's surrogate looks like early on):
                  item norms follow popularity
