@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ARLIB_AMD_LIB') or os.path.join(_HERE, 'lib', 'libarlib_amd.so')      # override: developer builds (e.g. `make prof`)
-ABI_VERSION = 29
+ABI_VERSION = 30
 _lib = None
 
 
@@ -134,6 +134,12 @@ _SIGS = {
     'arl_gan_threshold_f32': (C.c_int, [_vp, _i64, _i64, _f, _vp, _vp, _vp, _vp]),
     'arl_colsoftmax_target_workspace_bytes': (_i64, [_i64, _i64, _i64, _i32]),
     'arl_colsoftmax_target_loss_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'arl_kmeans_assign_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'arl_kmeans_chunk_rows': (_i64, []),
+    'arl_kmeans_update_workspace_bytes': (_i64, [_i64, _i64, _i64]),
+    'arl_kmeans_update_f32': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'arl_kmeans_sum_workspace_bytes': (_i64, []),
+    'arl_kmeans_sum_f64': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     'arl_comm_load': (C.c_int, [C.c_char_p]),
     'arl_comm_unique_id': (C.c_int, [_vp]),
     'arl_comm_init': (C.c_int, [_vp, _i64, _i64, _i64, C.POINTER(C.c_void_p)]),

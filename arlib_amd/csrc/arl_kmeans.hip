@@ -1,0 +1,285 @@
+// arl_kmeans.hip -- Lloyd's k-means for NCL's prototype step (reference recommender/NCL.py:52-73: e_step / run_kmeans) on gfx950.
+//
+// One iteration is  assign: label[n] = argmax_c (<x_n, c> - 1/2 |c|^2)  (the nearest centroid; |x_n|^2 does not depend on c), then
+// update: C[c] = mean of the rows labelled c.  The inertia of an assign pass is  sum_n |x_n|^2 - 2 sum_n best[n].
+//
+// Rules kept throughout:
+//   * the N x k scores are never stored: products run exact fp32 on v_mfma_f32_16x16x4_f32 in the layout of the all-rows InfoNCE kernel and of
+//     csm_stream_kernel: a wave keeps 16 POINTS in registers, the CENTROIDS and their bias -1/2 |c|^2 pass through LDS 64 rows at a time
+//     (double-buffered), every lane keeps a running (best, index) over the centroids it sees, the four lanes of a point reduce at the end;
+//   * ties go to the LOWER centroid index: a lane meets its centroids in ascending order and replaces its best only on a strict >, the
+//     cross-lane reduce prefers the lower index on equal scores;
+//   * the running index starts at 0, so a point whose scores are all NaN gets label 0 -- labels index the centroid table, never out of range;
+//   * every sum has a fixed order (no float atomics): the bias is a sequential row sum, a cluster's members are walked in ascending row order
+//     in chunks of kChunk rows whose partials are folded in chunk order, the inertia sums are double over fixed spans;
+//   * a cluster without members keeps its previous centroid bit for bit; the mean is sum / count (a division, not a product with 1 / count).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <math.h>
+#include "arlib_amd.h"
+
+#define KM_LAUNCH_CHECK()                                   \
+    do {                                                    \
+        hipError_t e__ = hipGetLastError();                 \
+        if (e__ != hipSuccess) return (int)e__;             \
+    } while (0)
+
+namespace {
+
+constexpr int kBlk = 256, kWaves = 4;
+constexpr int kChunk = 256;                  // member rows per partial sum of the update
+constexpr int kSumParts = 1024;              // spans of the double sums
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+
+// bias[c] = -1/2 |C[c]|^2, one thread per centroid, components in order
+__global__ __launch_bounds__(kBlk) void km_bias_kernel(const float *__restrict__ C, int K, int d, float *__restrict__ bias) {
+    const int c = blockIdx.x * kBlk + threadIdx.x;
+    if (c >= K) return;
+    const float4 *row = reinterpret_cast<const float4 *>(C + (size_t)c * d);
+    float s = 0.f;
+    for (int q = 0; q < d / 4; ++q) {
+        const float4 v = row[q];
+        s = fmaf(v.x, v.x, s); s = fmaf(v.y, v.y, s); s = fmaf(v.z, v.z, s); s = fmaf(v.w, v.w, s);
+    }
+    bias[c] = -0.5f * s;
+}
+
+// labels[n] = the centroid with the largest <x_n, c> + bias[c] (lowest index on a tie, 0 if no score compares), score[n] = that value
+template <int D>
+__global__ __launch_bounds__(kBlk) void km_assign_kernel(const float *__restrict__ X, int N, const float *__restrict__ Cn, const float *__restrict__ bias, int K,
+                                                          int32_t *__restrict__ labels, float *__restrict__ score) {
+    constexpr int Q = D / 4, LD = D + 4;
+    __shared__ __attribute__((aligned(16))) float tile[2][64 * LD];
+    __shared__ __attribute__((aligned(16))) float tbias[2][64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, g = lane >> 4;
+    const int r0 = (blockIdx.x * kWaves + wv) * 16;
+    float br[Q];
+    {
+        const int r = r0 + c;
+#pragma unroll
+        for (int i = 0; i < Q; i += 4) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < N) v = *reinterpret_cast<const float4 *>(X + (size_t)r * D + Q * g + i);
+            br[i] = v.x; br[i + 1] = v.y; br[i + 2] = v.z; br[i + 3] = v.w;
+        }
+    }
+    float best = -INFINITY;
+    int bi = 0;
+    const int nst = (K + 63) / 64;
+    // a stage is 64 x D floats = 16 D float4s over 256 threads; the NEXT stage is fetched into registers before the current one is consumed
+    // and goes to the other LDS buffer afterwards (macros, not lambdas: an array captured by reference stays in scratch memory)
+    constexpr int PF = 64 * (D / 4) / kBlk;
+    f32x4v pre[PF];
+    float pre_b = 0.f;
+    const int frow = tid / (D / 4), fq = (tid % (D / 4)) * 4;
+    constexpr int FSTEP = kBlk / (D / 4);
+#define KM_FETCH(ST)                                                                                                               \
+    do {                                                                                                                           \
+        _Pragma("unroll") for (int i = 0; i < PF; ++i) {                                                                           \
+            const int t = min((ST) * 64 + frow + i * FSTEP, K - 1);               /* clamped; rows past K are masked below */      \
+            pre[i] = *reinterpret_cast<const f32x4v *>(Cn + (size_t)t * D + fq);                                                   \
+        }                                                                                                                          \
+        if (tid < 64) pre_b = bias[min((ST) * 64 + tid, K - 1)];                                                                   \
+    } while (0)
+#define KM_STASH(BUF)                                                                                                              \
+    do {                                                                                                                           \
+        _Pragma("unroll") for (int i = 0; i < PF; ++i) *reinterpret_cast<f32x4v *>(&tile[BUF][(frow + i * FSTEP) * LD + fq]) = pre[i]; \
+        if (tid < 64) tbias[BUF][tid] = pre_b;                                                                                     \
+    } while (0)
+    KM_FETCH(0); KM_STASH(0);
+    __syncthreads();
+    for (int st = 0; st < nst; ++st) {
+        const int buf = st & 1;
+        if (st + 1 < nst) KM_FETCH(st + 1);
+        const float *T = tile[buf] + c * LD + Q * g;
+        // the stage's four 16-centroid tiles on four independent accumulators (the 16x16x4 form needs >= 2 to reach its issue rate)
+        f32x4v sc[4];
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub) sc[sub] = f32x4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < Q; i += 4) {
+            float4 a[4];
+#pragma unroll
+            for (int sub = 0; sub < 4; ++sub) a[sub] = *reinterpret_cast<const float4 *>(T + sub * 16 * LD + i);
+#pragma unroll
+            for (int sub = 0; sub < 4; ++sub) sc[sub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[sub].x, br[i], sc[sub], 0, 0, 0);
+#pragma unroll
+            for (int sub = 0; sub < 4; ++sub) sc[sub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[sub].y, br[i + 1], sc[sub], 0, 0, 0);
+#pragma unroll
+            for (int sub = 0; sub < 4; ++sub) sc[sub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[sub].z, br[i + 2], sc[sub], 0, 0, 0);
+#pragma unroll
+            for (int sub = 0; sub < 4; ++sub) sc[sub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[sub].w, br[i + 3], sc[sub], 0, 0, 0);
+        }
+        // register j of tile sub is centroid st * 64 + sub * 16 + 4 g + j against point r0 + c: ascending in (sub, j), so a strict > keeps the lower index
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub) {
+            const int cb = st * 64 + sub * 16 + 4 * g;
+            const float4 b4 = *reinterpret_cast<const float4 *>(&tbias[buf][sub * 16 + 4 * g]);
+            const float bj[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float v = sc[sub][j] + bj[j];
+                if (cb + j < K && v > best) { best = v; bi = cb + j; }
+            }
+        }
+        if (st + 1 < nst) KM_STASH(buf ^ 1);
+        __syncthreads();
+    }
+#undef KM_FETCH
+#undef KM_STASH
+    // the four lane groups of a point: the larger score, on equal scores the lower index (both lanes of a pair decide alike)
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {
+        const float v2 = __shfl_xor(best, off);
+        const int i2 = __shfl_xor(bi, off);
+        if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
+    }
+    if (g == 0 && r0 + c < N) {
+        labels[r0 + c] = bi;
+        score[r0 + c] = best;
+    }
+}
+
+// one workgroup per chunk of a cluster's member list: part[b][:] = sum of X[order[p]] over the chunk's positions p, ascending.
+// chunk_ptr[c] = chunks of the clusters before c; workgroups past chunk_ptr[K] have nothing to do.
+__global__ __launch_bounds__(kBlk) void km_segsum_kernel(const float *__restrict__ X, int N, int d, const int32_t *__restrict__ order, const int32_t *__restrict__ seg_ptr,
+                                                          const int32_t *__restrict__ chunk_ptr, int K, float *__restrict__ part) {
+    __shared__ float4 red[kBlk];
+    const int b = blockIdx.x;
+    if (b >= chunk_ptr[K]) return;
+    int lo = 0, hi = K - 1;                       // the last c with chunk_ptr[c] <= b; clusters without chunks share a value and are skipped
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (chunk_ptr[mid] <= b) lo = mid; else hi = mid - 1;
+    }
+    const int d4 = d >> 2, q = threadIdx.x % d4, rl = threadIdx.x / d4, lanes = kBlk / d4;
+    const long long p_begin = (long long)seg_ptr[lo] + (long long)(b - chunk_ptr[lo]) * kChunk;
+    long long p_end = p_begin + kChunk;
+    if (p_end > seg_ptr[lo + 1]) p_end = seg_ptr[lo + 1];
+    if (p_end > N) p_end = N;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long long p = (p_begin < 0 ? 0 : p_begin) + rl; p < p_end; p += lanes) {
+        const int r = order[p];
+        if ((unsigned)r >= (unsigned)N) continue;
+        const float4 v = *reinterpret_cast<const float4 *>(X + (size_t)r * d + 4 * q);
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (rl == 0) {
+        for (int j = 1; j < lanes; ++j) {
+            const float4 v = red[j * d4 + q];
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+        *reinterpret_cast<float4 *>(part + (size_t)b * d + 4 * q) = s;
+    }
+}
+
+// C_new[c] = (the cluster's partials in chunk order) / count, or C_prev[c] for a cluster without members
+__global__ __launch_bounds__(kBlk) void km_mean_kernel(const float *__restrict__ part, const int32_t *__restrict__ seg_ptr, const int32_t *__restrict__ chunk_ptr, int K, int d,
+                                                        const float *__restrict__ C_prev, float *__restrict__ C_new) {
+    const int e = blockIdx.x * kBlk + threadIdx.x;
+    if (e >= K * d) return;
+    const int c = e / d, col = e - c * d;
+    const int count = seg_ptr[c + 1] - seg_ptr[c];
+    if (count <= 0) { C_new[e] = C_prev[e]; return; }
+    float s = 0.f;
+    for (int j = chunk_ptr[c]; j < chunk_ptr[c + 1]; ++j) s += part[(size_t)j * d + col];
+    C_new[e] = s / (float)count;
+}
+
+// part[b] = sum of v (or v^2) over the b-th span in double: a thread's strided elements, then a tree over the workgroup
+__global__ __launch_bounds__(kBlk) void km_sum_partial_kernel(const float *__restrict__ v, long long n, long long span, int squared, double *__restrict__ part) {
+    __shared__ double red[kBlk];
+    const long long begin = (long long)blockIdx.x * span, end = min(n, begin + span);
+    double s = 0.0;
+    for (long long i = begin + threadIdx.x; i < end; i += kBlk) {
+        const double x = (double)v[i];
+        s += squared ? x * x : x;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = kBlk / 2; w > 0; w >>= 1) { if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w]; __syncthreads(); }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(kBlk) void km_sum_fold_kernel(const double *__restrict__ part, int n_part, double *__restrict__ out) {
+    __shared__ double red[kBlk];
+    double s = 0.0;
+    for (int b = threadIdx.x; b < n_part; b += kBlk) s += part[b];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = kBlk / 2; w > 0; w >>= 1) { if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w]; __syncthreads(); }
+    if (threadIdx.x == 0) out[0] = red[0];
+}
+
+bool km_width(int64_t d) { return d == 16 || d == 32 || d == 64 || d == 128; }
+
+template <int D>
+int km_assign_run(const float *X, int64_t N, const float *C, int64_t k, float *bias, int32_t *labels, float *score, hipStream_t st) {
+    hipLaunchKernelGGL(km_bias_kernel, dim3((unsigned)((k + kBlk - 1) / kBlk)), dim3(kBlk), 0, st, C, (int)k, D, bias);
+    KM_LAUNCH_CHECK();
+    hipLaunchKernelGGL((km_assign_kernel<D>), dim3((unsigned)((N + 63) / 64)), dim3(kBlk), 0, st, X, (int)N, C, (const float *)bias, (int)k, labels, score);
+    KM_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int arl_kmeans_assign_f32(const float *X, int64_t N, const float *C, int64_t k, int64_t d, float *bias, int32_t *labels, float *score, arl_stream_t stream) {
+    if (!X || !C || !bias || !labels || !score) return ARL_E_NULL;
+    if (!km_width(d)) return ARL_E_DIM;
+    if (N <= 0 || k <= 0) return ARL_E_ARG;
+    if (N > 0x7fffffffll / 128 || k > 0x7fffffffll / 128) return ARL_E_RANGE;
+    if (((uintptr_t)X | (uintptr_t)C) & 15) return ARL_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (d == 16) return km_assign_run<16>(X, N, C, k, bias, labels, score, st);
+    if (d == 32) return km_assign_run<32>(X, N, C, k, bias, labels, score, st);
+    if (d == 64) return km_assign_run<64>(X, N, C, k, bias, labels, score, st);
+    return km_assign_run<128>(X, N, C, k, bias, labels, score, st);
+}
+
+int64_t arl_kmeans_chunk_rows(void) { return kChunk; }
+
+int64_t arl_kmeans_update_workspace_bytes(int64_t N, int64_t k, int64_t d) {
+    if (N <= 0 || k <= 0 || !km_width(d)) return 0;
+    return (int64_t)sizeof(float) * (N / kChunk + k) * d;          // sum_c ceil(count_c / kChunk) <= N / kChunk + k
+}
+
+int arl_kmeans_update_f32(const float *X, int64_t N, int64_t d, const int32_t *order, const int32_t *seg_ptr, const int32_t *chunk_ptr, int64_t k, const float *C_prev,
+                          float *C_new, void *workspace, arl_stream_t stream) {
+    if (!X || !order || !seg_ptr || !chunk_ptr || !C_prev || !C_new || !workspace) return ARL_E_NULL;
+    if (!km_width(d)) return ARL_E_DIM;
+    if (N <= 0 || k <= 0 || C_prev == C_new) return ARL_E_ARG;
+    if (N > 0x7fffffffll / 128 || k > 0x7fffffffll / 128) return ARL_E_RANGE;
+    if (((uintptr_t)X | (uintptr_t)workspace) & 15) return ARL_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    float *part = (float *)workspace;
+    hipLaunchKernelGGL(km_segsum_kernel, dim3((unsigned)(N / kChunk + k)), dim3(kBlk), 0, st, X, (int)N, (int)d, order, seg_ptr, chunk_ptr, (int)k, part);
+    KM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_mean_kernel, dim3((unsigned)((k * d + kBlk - 1) / kBlk)), dim3(kBlk), 0, st, (const float *)part, seg_ptr, chunk_ptr, (int)k, (int)d, C_prev, C_new);
+    KM_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
+int64_t arl_kmeans_sum_workspace_bytes(void) { return (int64_t)sizeof(double) * kSumParts; }
+
+int arl_kmeans_sum_f64(const float *v, int64_t n, int32_t squared, double *out, void *workspace, arl_stream_t stream) {
+    if (!v || !out || !workspace) return ARL_E_NULL;
+    if (n <= 0) return ARL_E_ARG;
+    if (((uintptr_t)out | (uintptr_t)workspace) & 7) return ARL_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    long long parts = (n + 4095) / 4096;
+    if (parts > kSumParts) parts = kSumParts;
+    const long long span = (n + parts - 1) / parts;
+    parts = (n + span - 1) / span;
+    hipLaunchKernelGGL(km_sum_partial_kernel, dim3((unsigned)parts), dim3(kBlk), 0, st, v, (long long)n, span, (int)squared, (double *)workspace);
+    KM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(km_sum_fold_kernel, dim3(1), dim3(kBlk), 0, st, (const double *)workspace, (int)parts, out);
+    KM_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
+}  // extern "C"

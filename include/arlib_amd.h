@@ -616,6 +616,30 @@ int arl_colsoftmax_target_loss_f32(const float *Pu, int64_t U, const float *Pi, 
                                    float *loss, float *dPu, float *dPi, void *workspace, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Lloyd's k-means for NCL's prototypes (csrc/arl_kmeans.hip).  Replaces recommender/NCL.py:52-73 (e_step / run_kmeans: sklearn's KMeans on
+ * host copies of the tables; the commented faiss.Kmeans(gpu=True) of :61-66 is what the authors meant).  X [N, d] points, C [k, d]
+ * centroids, d in {16, 32, 64, 128} (else ARL_E_DIM), N, k >= 1 (else ARL_E_ARG) and <= 2^31 / 128 (else ARL_E_RANGE), X, C and
+ * workspaces 16-byte aligned (else ARL_E_ARG).  No N x k matrix is stored, no float atomics: every output is bit-identical from run to run.
+ *   assign : labels[n] = argmax_c (<x_n, c> - 1/2 |c|^2) = the nearest centroid, score[n] = that maximum; exact fp32 products on
+ *            v_mfma_f32_16x16x4_f32.  Equal scores: the LOWER index.  A point whose scores are all NaN: label 0 (never out of range).
+ *            bias [k]: scratch, receives -1/2 |c|^2.
+ *   update : C_new[c] = mean of the rows labelled c, or C_prev[c] bit for bit for a cluster without members.  The membership comes from the
+ *            caller: order [N] = row ids stably sorted by label, seg_ptr [k + 1] = first position of every cluster in `order`,
+ *            chunk_ptr [k + 1] = exclusive prefix sum of ceil(count_c / arl_kmeans_chunk_rows).  A cluster's rows are summed in ascending
+ *            order in chunks of that many rows, the chunks folded in order, the sum divided by the count.  C_new must not alias C_prev.
+ *   sum    : out[0] = sum of v[0..n) (squared != 0: of v^2) in double over fixed spans -- the two terms of the inertia
+ *            sum |x|^2 - 2 sum score.  workspace: arl_kmeans_sum_workspace_bytes bytes, 8-byte aligned like out.
+ * ---------------------------------------------------------------------------------------------- */
+int arl_kmeans_assign_f32(const float *X, int64_t N, const float *C, int64_t k, int64_t d, float *bias, int32_t *labels, float *score,
+                          arl_stream_t stream);
+int64_t arl_kmeans_chunk_rows(void);
+int64_t arl_kmeans_update_workspace_bytes(int64_t N, int64_t k, int64_t d);
+int arl_kmeans_update_f32(const float *X, int64_t N, int64_t d, const int32_t *order, const int32_t *seg_ptr, const int32_t *chunk_ptr, int64_t k,
+                          const float *C_prev, float *C_new, void *workspace, arl_stream_t stream);
+int64_t arl_kmeans_sum_workspace_bytes(void);
+int arl_kmeans_sum_f64(const float *v, int64_t n, int32_t squared, double *out, void *workspace, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Item-table exchange of the user-sharded step (no reference counterpart: main.py:19 pins one device).
  * One process per GPU.  arl_comm_unique_id (rank 0) -> the 128 bytes travel to every rank by any side channel (torch.distributed
  * broadcast) -> arl_comm_init on every rank.  arl_allreduce_item_f32 sum-all-reduces buf[0, n_elems) IN PLACE, asynchronously on `stream`,
