@@ -20,7 +20,9 @@ The BPR batch is global (same bit-exact sampler stream on every rank); a rank ta
 The collective and the kernel set are injected (`comm`, `kernels`) so the shard arithmetic can be exercised with
 world_size-2 gloo processes on CPU in the test-suite; the defaults are RCCL and the HIP kernels, nothing else.
 """
-import contextlib
+import ctypes as C
+import os
+from functools import partial
 
 import numpy as np
 import torch
@@ -65,7 +67,6 @@ class TorchDistComm:
     instead of the library all-reduce; everything else (the 3-float loss sums, CPU tensors) stays with torch.distributed."""
 
     def __init__(self, group=None, measure=False, item_exchange=None, n_chunks=4, direct_min_bytes=1 << 20):
-        import os
         import torch.distributed as dist
         self.dist, self.group = dist, group
         self.measure = bool(measure)
@@ -79,8 +80,6 @@ class TorchDistComm:
     # ---- native exchange (built lazily: needs an initialised process group to carry the communicator id)
     def _native_comm(self, device):
         if self._native is None:
-            import ctypes as C
-            import os
             from . import _lib
             L = _lib.lib()
             cand = os.path.join(os.path.dirname(torch.__file__), 'lib', 'librccl.so')          # the RCCL instance torch itself runs on
@@ -98,7 +97,6 @@ class TorchDistComm:
         return self._native
 
     def _direct(self, t):
-        import ctypes as C
         from . import _lib
         nat = self._native_comm(t.device)
         L, n = nat['L'], t.numel()
@@ -126,8 +124,8 @@ class TorchDistComm:
     def all_reduce_async(self, t):
         if self._use_direct(t):
             w = self._direct(t)
-            return _TimedWork(w, self) if self.measure else w
-        w = self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group, async_op=True)
+        else:
+            w = self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group, async_op=True)
         return _TimedWork(w, self) if self.measure else w
 
     def all_reduce(self, t):
@@ -197,15 +195,13 @@ class ShardedPropagationEngine:
     """Rank-local state + step() of the user-sharded LightGCN (mean of L+1 layers) + BPR/L2 + dense Adam."""
 
     def __init__(self, blocks, n_users, n_items, emb_size, n_layers, reg, lr, device, rank, world, table, chunk=512,
-                 comm=None, kernels=None, betas=(0.9, 0.999), eps=1e-8, skip_layer0=False, schedule='auto', two_streams=False):
+                 comm=None, kernels=None, betas=(0.9, 0.999), eps=1e-8, skip_layer0=False, schedule='auto'):
         if kernels is None:
             from . import ops as kernels         # the HIP kernels; fails loudly if libarlib_amd.so is missing
         self.k = kernels
         self.comm = comm if comm is not None else TorchDistComm()
         self.rank, self.world = rank, world
         self.skip0 = bool(skip_layer0)             # SimGCL: layers 1..L averaged (step_simgcl); LightGCN: 0..L (step / step_sparse)
-        self.two_streams = two_streams             # step_sparse: item-row and user-row kernels of a hop on two compute streams
-        self._side = None
         self.U, self.I, self.d, self.L = int(n_users), int(n_items), int(emb_size), int(n_layers)
         if self.L < 1:
             raise ValueError('the sharded engine is for graph models (n_layers >= 1)')
@@ -237,33 +233,29 @@ class ShardedPropagationEngine:
         self.ws = None
         self.sums = torch.zeros(3, dtype=torch.float32, device=self.device)
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=self.device)
-
-    def _side_stream(self):
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        return self._side
+        # created by the step that first needs them
+        self._sp_B = 0                                       # step_sparse: the batch size its state below was built for
+        self.flags = self.bits = self.dup_bits = self.C = self.Gc = self.ar = self.arB = self.hops = self._prep = None
+        self.S1 = self.S2 = self._gid = None                 # step_simgcl: the two views' layer means, global row ids for the in-kernel RNG
+        self.W = self.Wm = self.Wv = self.slope = None       # init_ngcf
 
     @classmethod
     def from_pairs(cls, pairs, n_users, n_items, emb_size, n_layers, reg, lr, device, rank, world, table, **kw):
         return cls(build_local_blocks(pairs, n_users, n_items, rank, world), n_users, n_items, emb_size, n_layers, reg, lr, device, rank, world, table, **kw)
 
     # one hop: dst = alpha * (A src) + beta * Z for user rows (exact) and item rows (all-reduced over ranks).
-    # Z is added on the item side BEFORE the reduction when `z_partial` (Z holds a per-rank partial, e.g. batch gradients),
-    # AFTER it otherwise (Z is replicated, e.g. the running layer sum).
-    def _hop(self, src, dst, alpha=1.0, beta=0.0, Z=None, z_partial=False):
+    # Z's item rows are replicated (complete on every rank), so they are added on the item side once, AFTER the reduction.
+    def _hop(self, src, dst, alpha=1.0, beta=0.0, Z=None):
         k, Ul = self.k, self.Ul
         di, du = dst[Ul:], dst[:Ul]
-        if beta != 0.0 and z_partial:
-            k.spmm(self.Ai, src, alpha, beta, Z[Ul:], out=di)
-        else:
-            k.spmm(self.Ai, src, alpha, out=di)
+        k.spmm(self.Ai, src, alpha, out=di)
         work = self.comm.all_reduce_async(di)
         if beta != 0.0:
             k.spmm(self.Au, src, alpha, beta, Z[:Ul], out=du)
         else:
             k.spmm(self.Au, src, alpha, out=du)
         work.wait()
-        if beta != 0.0 and not z_partial:
+        if beta != 0.0:
             di.add_(Z[Ul:], alpha=beta)
         return dst
 
@@ -275,26 +267,36 @@ class ShardedPropagationEngine:
 
     def forward_mean(self):
         """forward() for either encoder family: mean of layers 0..L (LightGCN) or 1..L (skip_layer0: SimGCL, unperturbed)."""
+        return self._layer_mean(self.S)
+
+    def _layer_mean(self, acc, after_hop=None):
+        """acc = the mean over layers of E0 propagated L times through Ea / Eb.  after_hop(h, dst): called on layer h + 1 right after its hop,
+        before it is summed and propagated further (SimGCL's perturbation)."""
         L = self.L
-        cur, nxt = self.Ea, self.Eb
-        self._hop(self.E0, cur)
-        if self.skip0:
-            self.S.copy_(cur)
-        else:
-            torch.add(self.E0, cur, out=self.S)
-        for _ in range(L - 1):
-            self._hop(cur, nxt)
-            self.S.add_(nxt)
-            cur, nxt = nxt, cur
-        self.S.mul_(1.0 / (L if self.skip0 else L + 1))
-        return self.S
+        cur, bufs = self.E0, (self.Ea, self.Eb)
+        for h in range(L):
+            dst = self._hop(cur, bufs[h % 2])
+            if after_hop is not None:
+                after_hop(h, dst)
+            if h:
+                acc.add_(dst)
+            elif self.skip0:
+                acc.copy_(dst)
+            else:
+                torch.add(self.E0, dst, out=acc)
+            cur = dst
+        return acc.mul_(1.0 / (L if self.skip0 else L + 1))
 
     def backward_mean(self, G):
         """dL/dE0 (local users + item replica) from dL/d(out) = G whose ITEM rows are per-rank partials: one I x d all-reduce completes
         them, then the Horner form of the transposed mean (A symmetric): L hops, each with its item-row exchange."""
-        L = self.L
         self.comm.all_reduce(G[self.Ul:])
-        bufs = [self.Ea, self.Eb]
+        return self._horner(G)
+
+    def _horner(self, G):
+        """The L hops of backward_mean on a G whose item rows are complete already."""
+        L = self.L
+        bufs = (self.Ea, self.Eb)
         acc = G
         if self.skip0:                                    # (1/L) sum_{k=1..L} A^k G
             for h in range(L - 1):
@@ -303,7 +305,7 @@ class ShardedPropagationEngine:
         s = 1.0 / (L + 1)                                 # (1/(L+1)) sum_{k=0..L} A^k G
         for h in range(L):
             a = s if h == L - 1 else 1.0
-            acc = self._hop(acc, bufs[h % 2], a, a, G, z_partial=False)
+            acc = self._hop(acc, bufs[h % 2], a, a, G)
         return acc
 
     # ---- CLeaR's surrogate step (attack/White/CLeaR.py:73-129) on the user-sharded layout -- BASELINE config 4 (SimGCL + CLeaR, user-sharded):
@@ -364,8 +366,7 @@ class ShardedPropagationEngine:
 
     def step_ngcf(self, u, p, n):
         k, L, Ul, d, dev = self.k, self.L, self.Ul, self.d, self.device
-        B = u.numel()
-        if not hasattr(self, 'W'):
+        if self.W is None:
             raise ValueError('step_ngcf: call init_ngcf(W1s, W2s) first')
         fused = hasattr(k, 'ngcf_dense_fwd') and d in getattr(k, 'NGCF_DENSE_WIDTHS', ())      # fp32-MFMA dense kernels (ops); the CPU test double has none
         saved = []
@@ -382,19 +383,8 @@ class ShardedPropagationEngine:
             acc += out_l
             ego = out_l
         out = acc.mul_(1.0 / (L + 1))
-        lu, lp, ln = self._local_batch(u, p, n)
-        if self.ws is None or self.ws.numel() < 4 * max(B, 1):
-            self.ws = torch.empty(4 * max(B, 1), dtype=torch.float32, device=dev)
-        k.bpr_l2_partial(out, Ul, lu, lp, ln, B, self.ws, self.sums)
-        self.comm.all_reduce(self.sums)
-        nu_, np_ = torch.sqrt(self.sums[1]), torch.sqrt(self.sums[2])
-        self.loss_out[0] = self.sums[0] / B
-        self.loss_out[1] = self.reg * (nu_ + np_)
-        self.loss_out[2] = nu_
-        self.loss_out[3] = np_
         G = torch.zeros_like(out)
-        if lu.numel():
-            k.bpr_l2_backward(out, Ul, lu, lp, ln, self.reg, self.loss_out, G, self.ws)
+        self._batch_loss(out, u, p, n, G)
         self.comm.all_reduce(G[Ul:])                                   # item rows: per-rank partials -> complete (replicated from here on)
         G.mul_(1.0 / (L + 1))                                          # d(out)/d(layer_k) = 1/(L+1) for every layer
         g_ego = G.clone()                                              # gradient reaching layer L's output
@@ -422,7 +412,7 @@ class ShardedPropagationEngine:
             gWs[l] = gW
             # g(ego_l) = A gP + gE (+ G/(L+1): layer l's own share of the mean); gP's item rows are replicas, so the hop's item-side partial
             # sums over local users are completed by its all-reduce and gE / G are added after it
-            back = self._hop(gP.contiguous(), torch.empty_like(gP), 1.0, 1.0, gE, z_partial=False)
+            back = self._hop(gP.contiguous(), torch.empty_like(gP), 1.0, 1.0, gE)
             g_ego = back.add_(G)
         self.t += 1
         k.adam_dense(self.E0, g_ego, self.m, self.v, self.lr, self.t, self.betas, self.eps)
@@ -434,11 +424,11 @@ class ShardedPropagationEngine:
         sel = (u >= self.u0) & (u < self.u1)
         return (u[sel] - self.u0).to(torch.int32).contiguous(), p[sel].contiguous(), n[sel].contiguous()
 
-    def step(self, u, p, n):
-        """One training iteration on the GLOBAL batch (device int32 tensors, identical on every rank)."""
-        k, Ul = self.k, self.Ul
-        B = u.numel()
-        out = self.forward()
+    def _batch_loss(self, out, u, p, n, G):
+        """BPR + L2 of the GLOBAL batch on the propagated table `out`, each rank summing over the samples whose user it owns: one 3-float
+        all-reduce makes the batch-wide mean and norms, loss_out is filled on every rank alike, and the local samples' dL/d(out) is added
+        into G (user rows complete, item rows this rank's partial)."""
+        k, Ul, B = self.k, self.Ul, u.numel()
         lu, lp, ln = self._local_batch(u, p, n)
         if self.ws is None or self.ws.numel() < 4 * max(B, 1):
             self.ws = torch.empty(4 * max(B, 1), dtype=torch.float32, device=self.device)
@@ -449,16 +439,20 @@ class ShardedPropagationEngine:
         self.loss_out[1] = self.reg * (nu + np_)
         self.loss_out[2] = nu
         self.loss_out[3] = np_
-        self.G.zero_()
         if lu.numel():
-            k.bpr_l2_backward(out, Ul, lu, lp, ln, self.reg, self.loss_out, self.G, self.ws)
+            k.bpr_l2_backward(out, Ul, lu, lp, ln, self.reg, self.loss_out, G, self.ws)
+
+    def step(self, u, p, n):
+        """One training iteration on the GLOBAL batch (device int32 tensors, identical on every rank)."""
+        out = self.forward()
+        self.G.zero_()
+        self._batch_loss(out, u, p, n, self.G)
         # backward, Horner form.  The user-side hop gathers ITEM rows of its operand, so G's item rows (per-rank partials:
         # each rank saw only its own samples) must be complete first: one more I x d all-reduce, after which G is
         # replicated on the item side and is added after each hop's reduction.
         acc = self.backward_mean(self.G)
         self.t += 1
-        if hasattr(k, 'adam_dense'):
-            k.adam_dense(self.E0, acc, self.m, self.v, self.lr, self.t, self.betas, self.eps)
+        self.k.adam_dense(self.E0, acc, self.m, self.v, self.lr, self.t, self.betas, self.eps)
         return self.loss_out
 
     # ---- sparse-batch step (same idea as PropagationEngine.step): L-1 full hops + a row-subset hop forward, a flag-masked
@@ -475,7 +469,7 @@ class ShardedPropagationEngine:
         B = u.numel()
         dev = self.device
         s = 1.0 / (L + 1)
-        if getattr(self, '_sp_B', None) != B:
+        if self._sp_B != B:
             self.flags = torch.zeros(self.Nl, dtype=torch.uint8, device=dev)
             self.bits = torch.zeros((self.Nl + 31) // 32, dtype=torch.int32, device=dev)
             self.dup_bits = torch.zeros_like(self.bits)
@@ -495,41 +489,18 @@ class ShardedPropagationEngine:
         item_rows_packed = rows_l[B:]
         # forward.  Software pipeline over hops: the item-row all-reduce of hop h runs behind A_u(h) AND A_i(h+1) -- the
         # item-side kernel of the next hop only gathers USER rows, which are local and already final.
-        # Optional (two_streams=True; measured on one rank's share of cfg2: 1.26 -> 1.34 ms wall per step, so OFF by default): A_i(h) on the
-        # main stream and A_u(h) on a side stream -- they read the same operand and write disjoint row blocks.  Events order exactly what depends:
-        #   A_i(h+1) after A_u(h) (user rows of the new layer);  A_u(h) after the all-reduce of hop h-1 (item rows of its operand).
-        two = self.two_streams and self.device.type == 'cuda'
-        if two:
-            main, side = torch.cuda.current_stream(), self._side_stream()
-            side.wait_stream(main)                             # the previous step's updates of E0 / the sparse state
-        on_side = (lambda: torch.cuda.stream(side)) if two else contextlib.nullcontext
         layers = [self.E0]
-        pending = ev_u = ev_ar = None
+        pending = None
         for h in range(L - 1):
             src, dst = layers[-1], self.hops[h]
-            if two and ev_u is not None:
-                main.wait_event(ev_u)                          # src's user rows come from the side stream
             k.spmm(self.Ai, src, out=dst[Ul:])                 # partial item rows (gathers user rows of src)
-            if not two:
-                # one compute stream: a collective's stream waits, at enqueue time, for everything the caller's stream holds -- so the exchange
-                # of hop h is enqueued right after A_i(h), BEFORE A_u(h) is, and runs behind A_u(h) and A_i(h+1)
-                if pending is not None:
-                    pending.wait()                             # src's item rows are complete from here on
-                pending = self.comm.all_reduce_async(dst[Ul:])
-                k.spmm(self.Au, src, out=dst[:Ul])             # exact user rows (gathers item rows of src)
-                layers.append(dst)
-                continue
-            with on_side():
-                if pending is not None:
-                    side.wait_event(ev_ar)
-                    pending.wait()
-                k.spmm(self.Au, src, out=dst[:Ul])
-                ev_u = side.record_event()
-            pending = self.comm.all_reduce_async(dst[Ul:])     # (main stream: after A_i(h) only -- A_u(h) is on the side stream)
-            ev_ar = main.record_event()
+            # one compute stream: a collective's stream waits, at enqueue time, for everything the caller's stream holds -- so the exchange
+            # of hop h is enqueued right after A_i(h), BEFORE A_u(h) is, and runs behind A_u(h) and A_i(h+1)
+            if pending is not None:
+                pending.wait()                                 # src's item rows are complete from here on
+            pending = self.comm.all_reduce_async(dst[Ul:])
+            k.spmm(self.Au, src, out=dst[:Ul])                 # exact user rows (gathers item rows of src)
             layers.append(dst)
-        if two and ev_u is not None:
-            main.wait_event(ev_u)                              # the row-subset hops below read the last layer's user rows
         X = layers[-1]
         # compact batch rows, already scaled by 1/(L+1): item rows = per-rank partial of the last hop + the layers' own rows, which are
         # replicas: layer j is contributed by rank j % world alone (its rows ride in the row-subset hop's epilogue); user rows = complete on the
@@ -560,8 +531,6 @@ class ShardedPropagationEngine:
         zu = self.flags[:Ul]
         acc = self.G
         pending, prev_items, prev_a = None, None, 1.0
-        ev_u = ev_ar = None
-        ev_g = main.record_event() if two else None                                # G, flags and bits are set (main stream)
         for h in range(L):
             last = h == L - 1
             a = s if last else 1.0
@@ -569,42 +538,21 @@ class ShardedPropagationEngine:
             if dst is acc:
                 dst = self.hops[(h + 1) % len(self.hops)]
             xf = self.bits if h == 0 else None
-            if two and ev_u is not None:
-                main.wait_event(ev_u)                                              # acc's user rows come from the side stream
             k.spmm_flagged(self.Ai, acc, xf, a, 0.0, None, None, out=dst[Ul:])     # partial item rows (gathers acc's user rows)
-            if not two:
-                # same order as in the forward: complete acc's item rows, enqueue THIS hop's exchange, then launch A_u -- the exchange of the
-                # last hop runs behind the user block's fused Adam hop
-                if pending is not None:
-                    pending.wait()
-                    k.rows_axpy_unique_(prev_items, self.G, item_rows_packed, prev_a, check_range=False, dup_bits=self.dup_bits)
-                pending, prev_items, prev_a = self.comm.all_reduce_async(dst[Ul:]), dst, a
-                if last:
-                    k.spmm_adam(self.Au, acc, a, a, self.G[:Ul], self.E0[:Ul], self.m[:Ul], self.v[:Ul], self.lr, self.t, self.betas, self.eps, zflags=zu)
-                else:
-                    k.spmm_flagged(self.Au, acc, xf, a, a, self.G[:Ul], zu, out=dst[:Ul])
-                acc = dst
-                continue
-            with on_side():
-                if pending is not None:                                            # complete acc's item rows before A_u reads them
-                    side.wait_event(ev_ar)
-                    pending.wait()
-                    k.rows_axpy_unique_(prev_items, self.G, item_rows_packed, prev_a, check_range=False, dup_bits=self.dup_bits)
-                else:
-                    side.wait_event(ev_g)
-                if last:
-                    k.spmm_adam(self.Au, acc, a, a, self.G[:Ul], self.E0[:Ul], self.m[:Ul], self.v[:Ul], self.lr, self.t, self.betas, self.eps, zflags=zu)
-                else:
-                    k.spmm_flagged(self.Au, acc, xf, a, a, self.G[:Ul], zu, out=dst[:Ul])
-                ev_u = side.record_event()
+            # same order as in the forward: complete acc's item rows, enqueue THIS hop's exchange, then launch A_u -- the exchange of the
+            # last hop runs behind the user block's fused Adam hop
+            if pending is not None:
+                pending.wait()
+                k.rows_axpy_unique_(prev_items, self.G, item_rows_packed, prev_a, check_range=False, dup_bits=self.dup_bits)
             pending, prev_items, prev_a = self.comm.all_reduce_async(dst[Ul:]), dst, a
-            ev_ar = main.record_event()
+            if last:
+                k.spmm_adam(self.Au, acc, a, a, self.G[:Ul], self.E0[:Ul], self.m[:Ul], self.v[:Ul], self.lr, self.t, self.betas, self.eps, zflags=zu)
+            else:
+                k.spmm_flagged(self.Au, acc, xf, a, a, self.G[:Ul], zu, out=dst[:Ul])
             acc = dst
         pending.wait()
         k.rows_axpy_unique_(prev_items, self.G, item_rows_packed, prev_a, check_range=False, dup_bits=self.dup_bits)
         k.adam_dense(self.E0[Ul:], acc[Ul:], self.m[Ul:], self.v[Ul:], self.lr, self.t, self.betas, self.eps)
-        if two:
-            main.wait_event(ev_u)                                                  # the user block's fused Adam hop (side stream) reads G / flags
         k.batch_rows_clear_(self.G, self.flags, self.bits, rows_l, check_range=False, dup_bits=self.dup_bits)      # clear the sparse state
         return self.loss_out
 
@@ -620,9 +568,7 @@ class ShardedPropagationEngine:
         if not self.skip0:
             raise ValueError('step_simgcl needs skip_layer0=True (SimGCL averages layers 1..L)')
         k, L, Ul, d, dev = self.k, self.L, self.Ul, self.d, self.device
-        B = u.numel()
-        inv = 1.0 / L
-        if not hasattr(self, 'S1'):
+        if self.S1 is None:
             self.S1, self.S2 = torch.zeros_like(self.S), torch.zeros_like(self.S)
 
         def noise(view, hop):
@@ -633,43 +579,21 @@ class ShardedPropagationEngine:
             item = torch.rand(self.I, d, generator=g, device=dev)
             return torch.cat([torch.rand(Ul, d, device=dev), item], 0)
 
-        def forward(view, acc):
-            cur, bufs = self.E0, [self.Ea, self.Eb]
-            for h in range(L):
-                dst = bufs[h % 2]
-                self._hop(cur, dst)
-                if view is not None:
-                    if noises is None and hasattr(k, 'simgcl_perturb_rng'):
-                        # noise drawn inside the kernel from (seed, step/view/hop stream, GLOBAL row id, column): the replicated item rows are
-                        # bit-identical on every rank by construction, and the draw does not depend on the world size
-                        if getattr(self, '_gid', None) is None:
-                            self._gid = torch.cat([torch.arange(self.u0, self.u1, device=dev), torch.arange(self.U, self.U + self.I, device=dev)]).to(torch.int32)
-                        k.simgcl_perturb_rng(dst, eps, 0x51AC1, (self.t * 2 + view) * L + h, out=dst, row_ids=self._gid)
-                    else:
-                        k.simgcl_perturb_(dst, noise(view, h), eps)
-                if h == 0:
-                    acc.copy_(dst)
-                else:
-                    acc.add_(dst)
-                cur = dst
-            return acc.mul_(inv)
+        def perturb(view, h, dst):
+            if noises is None and hasattr(k, 'simgcl_perturb_rng'):
+                # noise drawn inside the kernel from (seed, step/view/hop stream, GLOBAL row id, column): the replicated item rows are
+                # bit-identical on every rank by construction, and the draw does not depend on the world size
+                if self._gid is None:
+                    self._gid = torch.cat([torch.arange(self.u0, self.u1, device=dev), torch.arange(self.U, self.U + self.I, device=dev)]).to(torch.int32)
+                k.simgcl_perturb_rng(dst, eps, 0x51AC1, (self.t * 2 + view) * L + h, out=dst, row_ids=self._gid)
+            else:
+                k.simgcl_perturb_(dst, noise(view, h), eps)
 
-        out = forward(None, self.S)
-        v1, v2 = forward(0, self.S1), forward(1, self.S2)
+        out = self._layer_mean(self.S)
+        v1, v2 = self._layer_mean(self.S1, partial(perturb, 0)), self._layer_mean(self.S2, partial(perturb, 1))
         # ---- rec loss on the clean forward (as in step())
-        lu, lp, ln = self._local_batch(u, p, n)
-        if self.ws is None or self.ws.numel() < 4 * max(B, 1):
-            self.ws = torch.empty(4 * max(B, 1), dtype=torch.float32, device=dev)
-        k.bpr_l2_partial(out, Ul, lu, lp, ln, B, self.ws, self.sums)
-        self.comm.all_reduce(self.sums)
-        nu_, np_ = torch.sqrt(self.sums[1]), torch.sqrt(self.sums[2])
-        self.loss_out[0] = self.sums[0] / B
-        self.loss_out[1] = self.reg * (nu_ + np_)
-        self.loss_out[2] = nu_
-        self.loss_out[3] = np_
         self.G.zero_()
-        if lu.numel():
-            k.bpr_l2_backward(out, Ul, lu, lp, ln, self.reg, self.loss_out, self.G, self.ws)
+        self._batch_loss(out, u, p, n, self.G)
         self.comm.all_reduce(self.G[Ul:])                                        # item rows: per-rank partials -> complete
         # ---- contrastive loss: unique users of the GLOBAL batch (rows live on their owners), unique positive items (replicated)
         uidx = torch.unique(u.long())
@@ -691,10 +615,7 @@ class ShardedPropagationEngine:
         self.G.index_add_(0, Ul + iidx, (di1 + di2) * cl_rate)                    # identical on every rank, after the reduction
         # ---- one backward pass for the three forwards, Adam on the local block + the item replica
         self.t += 1
-        acc, bufs = self.G, [self.Ea, self.Eb]
-        for h in range(L - 1):
-            acc = self._hop(acc, bufs[h % 2], 1.0, 1.0, self.G)
-        grad = self._hop(acc, bufs[(L - 1) % 2], inv)
+        grad = self._horner(self.G)
         k.adam_dense(self.E0, grad, self.m, self.v, self.lr, self.t, self.betas, self.eps)
         return self.loss_out, cl_loss
 
@@ -754,6 +675,8 @@ class ShardedPGA:
         self.E0 = torch.cat([table[self.u0:self.u1], table[self.Up:]], 0).to(self.device).contiguous()
         self.fake_rows = torch.arange(self.f0, self.Ul, dtype=torch.int32, device=self.device)
         self.S = None
+        self.dinv = self._dcol = None                # this step's D^-1/2 (_degrees)
+        self.last_block = None                       # owner: the F x I block gradient of the latest step
 
     def set_block(self, S):
         """S [F, I] on the owner (ignored elsewhere)."""

@@ -136,6 +136,55 @@ def test_sharded_engine_gloo_matches_single_process_oracle(world, sparse, deferr
     assert (ret['top10'] == ref_idx).mean() > 0.995
 
 
+def sparse_shapes_problem(L, sizes, d=16):
+    """small_problem's graph and table at another depth, with one batch per entry of `sizes`: a change of the batch size between two steps
+    makes step_sparse rebuild its sparse state."""
+    U, I, d, _, pairs, E0, _ = small_problem(d)
+    rng = np.random.default_rng(3)
+    batches = []
+    for B in sizes:
+        sel = rng.integers(0, len(pairs), B)
+        batches.append((pairs[sel, 0].copy(), pairs[sel, 1].copy(), rng.integers(0, I, B).astype(np.int32)))
+    return U, I, d, L, pairs, E0, batches
+
+
+def _sparse_shapes_worker(rank, world, port, ret, L, sizes, deferred):
+    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import torch.distributed as dist
+    import cpu_kernels_shim as shim
+    from arlib_amd.dist_engine import ShardedPropagationEngine
+    os.environ['MASTER_ADDR'] = '127.0.0.1'; os.environ['MASTER_PORT'] = str(port)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    torch.set_num_threads(1)
+    U, I, d, L, pairs, E0, batches = sparse_shapes_problem(L, sizes)
+    eng = ShardedPropagationEngine.from_pairs(pairs, U, I, d, L, 1e-4, 0.005, 'cpu', rank, world, torch.from_numpy(E0), kernels=shim,
+                                              comm=DeferredPoisonGloo() if deferred else None)
+    losses = []
+    for u, p, n in batches:
+        lo = eng.step_sparse(torch.from_numpy(u), torch.from_numpy(p), torch.from_numpy(n))
+        losses.append(float(lo[0] + lo[1]))
+    full = eng.gather_full_table().numpy()
+    if rank == 0:
+        ret['table'], ret['losses'] = full, losses
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize('deferred', [False, True])
+@pytest.mark.parametrize('world', [2, 3])
+@pytest.mark.parametrize('L', [1, 2, 4, 5])
+def test_sharded_sparse_step_depths_and_batch_size_changes(L, world, deferred):
+    """step_sparse away from L = 3 and one batch size: L = 1 (no full hop, nothing pending when the batch rows are built), L = 2 (the one full
+    hop hands its exchange straight to the batch rows), L >= 4 (hop buffers besides Ea / Eb), and batch sizes 256, 100, 256, 1 (the sparse
+    state is rebuilt at every change)."""
+    sizes = (256, 100, 256, 1)
+    U, I, d, L, pairs, E0, batches = sparse_shapes_problem(L, sizes)
+    ref_table, ref_losses = oracle_run(U, I, d, L, pairs, E0, batches)
+    ret = mp.Manager().dict()
+    mp.spawn(_sparse_shapes_worker, args=(world, free_port(), ret, L, sizes, deferred), nprocs=world, join=True)
+    assert np.allclose(ret['losses'], ref_losses, rtol=RTOL, atol=0)
+    assert rel_err(ret['table'], ref_table) < RTOL
+
+
 def simgcl_problem():
     U, I, d, _, pairs, E0, batches = small_problem()
     rng = np.random.default_rng(5)

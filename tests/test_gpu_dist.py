@@ -114,6 +114,43 @@ def test_sharded_engine_two_ranks_hip_kernels(sparse, d, schedule, comm):
     assert rel_err(ret['table'], ref_table) < RTOL
 
 
+def _sparse_shapes_worker(rank, world, port, ret, L, sizes, d, schedule, comm):
+    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import torch.distributed as dist
+    from arlib_amd.dist_engine import ShardedPropagationEngine
+    from test_dist_cpu import sparse_shapes_problem
+    os.environ['MASTER_ADDR'] = '127.0.0.1'; os.environ['MASTER_PORT'] = str(port)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    torch.cuda.set_device(0)
+    U, I, d, L, pairs, E0, batches = sparse_shapes_problem(L, sizes, d)
+    eng = ShardedPropagationEngine.from_pairs(pairs, U, I, d, L, 1e-4, 0.005, 'cuda:0', rank, world, torch.from_numpy(E0), comm=_comm(comm), schedule=schedule)
+    assert (eng.Au.blocked is not None) == (schedule == 'blocked')
+    losses = []
+    for u, p, n in batches:
+        lo = eng.step_sparse(torch.from_numpy(u).cuda(), torch.from_numpy(p).cuda(), torch.from_numpy(n).cuda())
+        losses.append(float(lo[0] + lo[1]))
+    full = eng.gather_full_table().cpu().numpy()
+    if rank == 0:
+        ret['table'], ret['losses'] = full, losses
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize('schedule', ['csr', 'blocked'])
+@pytest.mark.parametrize('L', [1, 2, 4])
+def test_sharded_sparse_step_depths_and_batch_size_changes_hip_kernels(L, schedule):
+    """step_sparse away from L = 3 and one batch size (see the CPU test of the same name): L = 1, 2, 4 with batch sizes 256, 100, 256 at d = 64,
+    on the CSR hops and on the blocked plan's, under the comm double whose reduction lands only inside wait()."""
+    if not torch.cuda.is_available():
+        pytest.fail('GPU tests need a GPU')
+    from test_dist_cpu import sparse_shapes_problem
+    sizes, d = (256, 100, 256), 64
+    U, I, d, L, pairs, E0, batches = sparse_shapes_problem(L, sizes, d)
+    ref_table, ref_losses = oracle_run(U, I, d, L, pairs, E0, batches)
+    ret = _spawn(_sparse_shapes_worker, (L, sizes, d, schedule, 'deferred'))
+    assert np.allclose(ret['losses'], ref_losses, rtol=RTOL, atol=0)
+    assert rel_err(ret['table'], ref_table) < RTOL
+
+
 def _simgcl_worker(rank, world, port, ret, comm='staged'):
     sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import torch.distributed as dist
