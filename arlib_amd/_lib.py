@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ARLIB_AMD_LIB') or os.path.join(_HERE, 'lib', 'libarlib_amd.so')      # override: developer builds (e.g. `make prof`)
-ABI_VERSION = 30
+ABI_VERSION = 31
 _lib = None
 
 
@@ -41,6 +41,8 @@ _SIGS = {
     'arl_mt_seed': (C.c_int, [_vp, _vp, _i64]),
     'arl_sampler_shuffle': (C.c_int, [_vp, _vp, _i64]),
     'arl_mt_sample_range': (C.c_int, [_vp, _i64, _i64, C.c_int32, _vp, _vp]),
+    'arl_goat_item_sample_scratch_words': (_i64, [_i64, _i64, _i64]),
+    'arl_goat_item_sample': (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, C.c_double, _i64, _vp, _vp, _vp, _vp, _vp]),
     'arl_sampler_next_batch': (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     'arl_norm_adj_values_f32': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'arl_norm_adj_values_coo_f32': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
@@ -140,6 +142,8 @@ _SIGS = {
     'arl_kmeans_update_f32': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'arl_kmeans_sum_workspace_bytes': (_i64, []),
     'arl_kmeans_sum_f64': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    'arl_corating_max_items': (_i64, []),
+    'arl_corating_degree_i32': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     'arl_comm_load': (C.c_int, [C.c_char_p]),
     'arl_comm_unique_id': (C.c_int, [_vp]),
     'arl_comm_init': (C.c_int, [_vp, _i64, _i64, _i64, C.POINTER(C.c_void_p)]),

@@ -90,7 +90,7 @@ inline bool user_has_item(const int64_t *rowptr, const int32_t *items, int64_t r
 
 extern "C" {
 
-int arl_abi_version(void) { return 30; }
+int arl_abi_version(void) { return 31; }
 
 int arl_mt_seed(uint32_t *mt_state, const uint32_t *key, int64_t key_len) {
     if (!mt_state || !key) return ARL_E_NULL;
@@ -150,6 +150,148 @@ int arl_mt_sample_range(uint32_t *mt_state, int64_t n, int64_t k, int32_t use_po
             while ((seen[j >> 5] >> (j & 31)) & 1u) j = rng.below((uint32_t)n);
             seen[j >> 5] |= 1u << (j & 31);
             out[i] = (int32_t)j;
+        }
+    }
+    return ARL_OK;
+}
+
+}  // extern "C"
+
+// ---- GOAT's itemSample (reference attack/Gray/GOAT.py:105-135) ----
+namespace {
+
+// The r-th (0-based) id of range(n) minus the ascending, duplicate-free ids excl[0..n_excl): r plus the number of excluded ids at or below it.
+// excl[t] - t never decreases, so the count is the first t with excl[t] - t > r.
+inline int32_t nth_remaining(int64_t r, const int32_t *excl, int64_t n_excl) {
+    int64_t lo = 0, hi = n_excl;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if ((int64_t)excl[mid] - mid <= r) lo = mid + 1; else hi = mid;
+    }
+    return (int32_t)(r + lo);
+}
+
+// random.sample(pool, m) of CPython 3.10 for the pool above (n ids), written to out[0..m).  idx: n int32 (pool form), seen: (n + 31) / 32 words,
+// all zero on entry and on return (selection form).
+void sample_remaining(PyMersenne &rng, int64_t n, int64_t m, const int32_t *excl, int64_t n_excl, int32_t *out, int32_t *idx, uint32_t *seen) {
+    int64_t setsize = 21;
+    if (m > 5) {
+        const double e = std::ceil(std::log((double)(m * 3)) / std::log(4.0));       // math.log(k * 3, 4) = log(x) / log(4)
+        int64_t p = 1;
+        for (int64_t t = 0; t < (int64_t)e; ++t) p *= 4;
+        setsize += p;
+    }
+    if (n <= setsize) {
+        for (int64_t i = 0; i < n; ++i) idx[i] = (int32_t)i;
+        for (int64_t i = 0; i < m; ++i) {
+            const uint32_t j = rng.below((uint32_t)(n - i));
+            out[i] = nth_remaining(idx[j], excl, n_excl);
+            idx[j] = idx[n - i - 1];
+        }
+    } else {
+        for (int64_t i = 0; i < m; ++i) {
+            uint32_t j = rng.below((uint32_t)n);
+            while ((seen[j >> 5] >> (j & 31)) & 1u) j = rng.below((uint32_t)n);
+            seen[j >> 5] |= 1u << (j & 31);
+            idx[i] = (int32_t)j;                                                      // remembered to clear its bit below
+            out[i] = nth_remaining(j, excl, n_excl);
+        }
+        for (int64_t i = 0; i < m; ++i) seen[(uint32_t)idx[i] >> 5] = 0u;
+    }
+}
+
+// sorted, duplicate-free union of a (sorted, duplicate-free, na ids) and b (nb ids in any order, sorted in place) into dst; returns its length
+int64_t merge_sorted(const int32_t *a, int64_t na, int32_t *b, int64_t nb, int32_t *dst) {
+    std::sort(b, b + nb);
+    int64_t i = 0, j = 0, n = 0;
+    while (i < na || j < nb) {
+        int32_t v;
+        if (j >= nb || (i < na && a[i] <= b[j])) v = a[i++]; else v = b[j++];
+        if (n == 0 || dst[n - 1] != v) dst[n++] = v;
+    }
+    return n;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t arl_goat_item_sample_scratch_words(int64_t n_items, int64_t k, int64_t n_targets) {
+    if (n_items < 0 || k < 0 || n_targets < 0) return ARL_E_ARG;
+    return n_items + (n_items + 31) / 32 + 4 * (k + n_targets) + 16;
+}
+
+int arl_goat_item_sample(uint32_t *mt_state, const int64_t *rowptr, const int32_t *items, int64_t n_users, int64_t n_items,
+                         const double *int_num, const int32_t *targets, int64_t n_targets, int64_t n_fake, int64_t k, double min_items,
+                         int64_t thr, int32_t *out_s, int32_t *out_f, uint8_t *out_real, int32_t *out_user, int32_t *scratch) {
+    if (!mt_state || !rowptr || !int_num || !out_user || !scratch || (n_targets > 0 && !targets)) return ARL_E_NULL;
+    if (n_users < 1 || n_items < 1 || n_targets < 0 || n_fake < 0 || k < 1) return ARL_E_ARG;
+    if (n_users > 0x7fffffffll || n_items > 0x7fffffffll) return ARL_E_RANGE;
+    if ((double)(k + n_targets) > 0.4 * (double)n_items) return ARL_E_RANGE;          // past it CPython's set no longer iterates in ascending order
+    if (mt_state[624] > 624) return ARL_E_ARG;
+    const int64_t ks = (int64_t)((double)k * 0.3), kf_walk = (int64_t)((double)k * 0.7), kf = k - ks;       // int(k * 0.3), int(k * 0.7)
+    if (n_fake > 0 && ((ks > 0 && !out_s) || !out_f || !out_real)) return ARL_E_NULL;
+    for (int64_t t = 0; t < n_targets; ++t)
+        if (targets[t] < 0 || targets[t] >= n_items) return ARL_E_ARG;
+    // scratch: idx [n_items] | seen [(n_items + 31) / 32] | base, excl, walk, tmp [k + n_targets each]
+    const int64_t cap = k + n_targets;
+    int32_t *idx = scratch;
+    uint32_t *seen = reinterpret_cast<uint32_t *>(scratch + n_items);
+    int32_t *base = scratch + n_items + (n_items + 31) / 32, *excl = base + cap, *walk = excl + cap, *tmp = walk + cap;
+    for (int64_t w = 0; w < (n_items + 31) / 32; ++w) seen[w] = 0u;
+    PyMersenne rng(mt_state);
+    out_user[0] = -1;
+    if (n_fake == 0) return ARL_OK;
+
+    // while realUser.sum() < O_u * itemNum: realUser = interact[randint(0, U - 1)] -- realUser is reset per call, so only the first row draws.
+    // The reference never returns when no user has that many items; here that is an argument error, found before anything is drawn.
+    if (min_items > 0.0) {
+        bool any = false;
+        for (int64_t u = 0; u < n_users && !any; ++u) any = (double)(rowptr[u + 1] - rowptr[u]) >= min_items;
+        if (!any) return ARL_E_ARG;
+    }
+    int32_t user = -1;
+    double have = 0.0;
+    while (have < min_items) {
+        user = (int32_t)rng.below((uint32_t)n_users);
+        have = (double)(rowptr[user + 1] - rowptr[user]);
+    }
+    out_user[0] = user;
+    const int32_t *ub = user >= 0 ? items + rowptr[user] : nullptr, *ue = user >= 0 ? items + rowptr[user + 1] : nullptr;
+    // the walk over the real user's items: I_s first, else (`elif`) I_f; walk[0..ns) = I_s, walk[ns..ns + nf) = I_f
+    int64_t ns = 0, nf = 0;
+    const double thr_s = (double)thr, thr_f = (double)thr / 3.0;
+    for (const int32_t *p = ub; p < ue; ++p) {
+        if (*p < 0 || *p >= n_items) continue;
+        if (int_num[*p] > thr_s && ns < ks) walk[ns++] = *p;
+        else if (int_num[*p] > thr_f && nf < kf_walk) tmp[nf++] = *p;
+    }
+    for (int64_t t = 0; t < nf; ++t) walk[ns + t] = tmp[t];
+    if (ns + nf > k) return ARL_E_ARG;                                                // cannot happen: int(0.3 k) + int(0.7 k) <= k
+    // base = sorted union of the targets and the walk's items
+    for (int64_t t = 0; t < n_targets; ++t) tmp[t] = targets[t];
+    const int64_t nt = merge_sorted(nullptr, 0, tmp, n_targets, excl);
+    for (int64_t t = 0; t < ns + nf; ++t) tmp[t] = walk[t];
+    const int64_t n_base = merge_sorted(excl, nt, tmp, ns + nf, base);
+
+    for (int64_t f = 0; f < n_fake; ++f) {
+        int32_t *rs = out_s + f * ks, *rf = out_f + f * kf;
+        for (int64_t t = 0; t < ns; ++t) rs[t] = walk[t];
+        for (int64_t t = 0; t < nf; ++t) rf[t] = walk[ns + t];
+        const int32_t *ex = base;
+        int64_t n_ex = n_base;
+        if (ns < ks) {                                                                 // while len(I_s) < int(k * 0.3): one random.sample fills it
+            sample_remaining(rng, n_items - n_ex, ks - ns, ex, n_ex, rs + ns, idx, seen);
+            for (int64_t t = ns; t < ks; ++t) tmp[t - ns] = rs[t];
+            n_ex = merge_sorted(base, n_base, tmp, ks - ns, excl);
+            ex = excl;
+        }
+        if (nf < kf)                                                                   // while len(I_f) + len(I_s) < k
+            sample_remaining(rng, n_items - n_ex, kf - nf, ex, n_ex, rf + nf, idx, seen);
+        uint8_t *rr = out_real + f * k;                                                // realUser[I_s + I_f]
+        for (int64_t t = 0; t < k; ++t) {
+            const int32_t it = t < ks ? rs[t] : rf[t - ks];
+            rr[t] = (ub && std::binary_search(ub, ue, it)) ? 1 : 0;
         }
     }
     return ARL_OK;

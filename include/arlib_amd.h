@@ -51,6 +51,23 @@ int arl_sampler_shuffle(uint32_t *mt_state, int32_t *pairs, int64_t nnz);
  * contrastive encoders draw (recommender/SGL.py:281-299: edge / node dropout).  use_pool: the caller evaluates CPython's
  * set-size rule (n <= 21 + (k > 5 ? 4 ** ceil(log(3k, 4)) : 0)).  scratch: n int32 (pool form) or (n+31)/32 int32. */
 int arl_mt_sample_range(uint32_t *mt_state, int64_t n, int64_t k, int32_t use_pool, int32_t *out, int32_t *scratch);
+/* attack/Gray/GOAT.py:105-135  one itemSample(k, O_u, O_g, O_i) call for n_fake fake users on the caller's MT19937 state.
+ *   rowptr / items : the interaction matrix as CSR (ascending item ids per user);  int_num [n_items]: itemIntNum as doubles;
+ *   targets [n_targets]: the target items (excluded from the fill draws);  min_items = O_u * n_items and thr = int(O_i * n_users), both
+ *   evaluated by the caller as Python evaluates them.
+ * realUser starts empty per CALL: the first fake row draws randint(0, n_users - 1) until a user with degree >= min_items comes (the caller
+ * should make sure one exists, where the reference would never return: without one this returns ARL_E_ARG before it draws), every later row
+ * keeps that user.  Its items are walked ascending into I_s
+ * (int_num > thr, fewer than ks = int(0.3 k) so far) or else I_f (int_num > thr / 3.0, fewer than int(0.7 k)); I_s is filled to ks, then I_f
+ * until both hold k, each by one random.sample(pool, m) over the ASCENDING remaining ids (range(n_items) minus targets, I_s, I_f): the
+ * pool is not built, its r-th id is found by a search in the sorted excluded ids.  That is CPython's order of the set only while
+ * k + n_targets <= 0.4 * n_items (else ARL_E_RANGE: the caller evaluates the reference's expression in Python).
+ *   out_s [n_fake][ks], out_f [n_fake][k - ks], out_real [n_fake][k] (1 where the candidate is an item of the real user), out_user [1];
+ *   scratch: arl_goat_item_sample_scratch_words(n_items, k, n_targets) int32 words, no initialisation needed. */
+int64_t arl_goat_item_sample_scratch_words(int64_t n_items, int64_t k, int64_t n_targets);
+int arl_goat_item_sample(uint32_t *mt_state, const int64_t *rowptr, const int32_t *items, int64_t n_users, int64_t n_items,
+                         const double *int_num, const int32_t *targets, int64_t n_targets, int64_t n_fake, int64_t k, double min_items,
+                         int64_t thr, int32_t *out_s, int32_t *out_f, uint8_t *out_real, int32_t *out_user, int32_t *scratch);
 /* util/sampler.py:12-29  one batch: positives pairs[begin..begin+count), one negative per positive drawn
  * by choice(item_list) with rejection against training_set_u[user] (given as a CSR with sorted item
  * ids; users >= memb_rows have an empty set, which is what the reference's defaultdict gives users
@@ -638,6 +655,20 @@ int arl_kmeans_update_f32(const float *X, int64_t N, int64_t d, const int32_t *o
                           const float *C_prev, float *C_new, void *workspace, arl_stream_t stream);
 int64_t arl_kmeans_sum_workspace_bytes(void);
 int arl_kmeans_sum_f64(const float *v, int64_t n, int32_t squared, double *out, void *workspace, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * GOAT's co-rating degree (csrc/arl_corating.hip).  Replaces attack/Gray/GOAT.py:37-39 (interact.T @ interact, every stored entry set to 1,
+ * column sums): out[j] = the number of distinct items i (j included) that share a user with item j, 0 for an item nobody rated.  The product
+ * is never formed: a workgroup owns one item and a bitmap of n_items bits in LDS, ORs the items of every user of j into it and popcounts.
+ *   u_rowptr [n_users + 1], u_col [nnz]     : the interaction matrix as CSR (users -> items; any order within a row, repeats allowed);
+ *   i_colptr [n_items + 1], i_row [nnz]     : the same matrix as CSC (items -> users);
+ *   order [n_items] (optional, NULL = index order): a permutation of the items, the order in which workgroups take them (heaviest first);
+ *   out [n_items] int32: every word is written exactly once; no other global memory is written, no workspace is needed.
+ * n_items > arl_corating_max_items() (the 160 KiB of LDS minus the kernel's 16 words, in bits) or n_users >= 2^31: ARL_E_RANGE before any
+ * launch.  Ids outside [0, n_users) / [0, n_items) are skipped.  Integer result: bit-identical from run to run. */
+int64_t arl_corating_max_items(void);
+int arl_corating_degree_i32(const int64_t *u_rowptr, const int32_t *u_col, const int64_t *i_colptr, const int32_t *i_row, int64_t n_users,
+                            int64_t n_items, const int32_t *order, int32_t *out, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Item-table exchange of the user-sharded step (no reference counterpart: main.py:19 pins one device).
