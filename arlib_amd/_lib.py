@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ARLIB_AMD_LIB') or os.path.join(_HERE, 'lib', 'libarlib_amd.so')      # override: developer builds (e.g. `make prof`)
-ABI_VERSION = 31
+ABI_VERSION = 32
 _lib = None
 
 
@@ -27,12 +27,6 @@ class arl_blocked(C.Structure):
     _fields_ = [('n_waves', C.c_int64), ('rows_per_wave', C.c_int64), ('loads_in_flight', C.c_int64), ('wave_ptr', C.c_void_p), ('wave_rows', C.c_void_p), ('rec_col', C.c_void_p),
                 ('rec_val', C.c_void_p), ('n_split', C.c_int64), ('split_row', C.c_void_p), ('split_first', C.c_void_p), ('split_count', C.c_void_p),
                 ('partial', C.c_void_p), ('waves_per_group', C.c_int64)]
-
-
-class arl_tiled(C.Structure):
-    _fields_ = [('n_sweeps', C.c_int64), ('n_slots', C.c_int64), ('cap', C.c_int64), ('n_cb', C.c_int64), ('nnz', C.c_int64),
-                ('n_groups', C.c_int64), ('bin_rows', C.c_void_p), ('seg_ptr', C.c_void_p), ('e_col', C.c_void_p), ('e_val', C.c_void_p),
-                ('e_row', C.c_void_p)]
 
 
 _vp, _i64, _i32, _f = C.c_void_p, C.c_int64, C.c_int32, C.c_float
@@ -59,8 +53,6 @@ _SIGS = {
     'arl_lpt_deal': (C.c_int, [_i64, _vp, _i64, _i64, _vp, _vp]),
     'arl_syn_v1_pairs': (_i64, [_i64, _i64, C.c_double, C.c_uint64, C.c_double, _i64, _i64, _vp, _i64]),
     'arl_graph_digest': (C.c_uint64, [_vp, _i64]),
-    'arl_spmm_tiled_f32': (C.c_int, [C.POINTER(arl_tiled), _vp, _i64, _f, _f, _vp, _vp, _vp, _vp]),
-    'arl_spmm_tiled_adam_f32': (C.c_int, [C.POINTER(arl_tiled), _vp, _i64, _f, _f, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i64, _vp]),
     'arl_spmm_csr_flagged_f32': (C.c_int, [C.POINTER(arl_csr), _vp, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp]),
     'arl_spmm_csr_rows_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'arl_spmm_csr_rows_f32': (C.c_int, [C.POINTER(arl_csr), _vp, _i64, _vp, _i64, _i64, _vp, _i64, _f, _vp, _vp, _vp, _vp]),

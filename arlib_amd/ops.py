@@ -423,20 +423,24 @@ def auto_blocked(graph, d, split=None, force=False, rows_per_wave=32, small_laun
     return graph
 
 
-def _spmm_dispatch(A, d, blocked_call, csr_call, rows_from=0):
+def _spmm_dispatch(A, d, blocked_call, csr_call, tag, rows_from=0):
     """Run one full-table SpMM: through the blocked plan (+ its hub rows through the chunked CSR kernel) when the graph has one
     and d = 64 or 128, else through the CSR kernel.  The callables take the ctypes struct pointer.  rows_from > 0: the caller does not
-    read output rows below it -- launches of the plan that only produce such rows are skipped (the CSR schedule ignores the hint)."""
+    read output rows below it -- launches of the plan that only produce such rows are skipped (the CSR schedule ignores the hint).
+    The launches are bracketed with EVENT_HOOK under `tag` when a hook is installed."""
+    tok = EVENT_HOOK.begin(tag) if EVENT_HOOK is not None else None
     bp = A.blocked
     if bp is None or d not in (64, 128):
         csr_call(C.byref(A._struct(d)))
-        return
-    for k in range(len(bp.sets)):
-        if bp.sets[k]['hi'] <= rows_from:
-            continue
-        blocked_call(C.byref(bp.struct(k, d)))
-    if bp.hub is not None:
-        csr_call(C.byref(bp.hub._struct(d)))
+    else:
+        for k in range(len(bp.sets)):
+            if bp.sets[k]['hi'] <= rows_from:
+                continue
+            blocked_call(C.byref(bp.struct(k, d)))
+        if bp.hub is not None:
+            csr_call(C.byref(bp.hub._struct(d)))
+    if tok is not None:
+        EVENT_HOOK.end(tok)
 
 
 def norm_vals_coo(erow, col, w, dinv):
@@ -636,31 +640,50 @@ def _check_xy(A, X, name='X', rows=None):
     return d
 
 
+def _check_flags(t, n, name):
+    _dev(t, torch.uint8, name, 1)
+    if t.numel() != n:
+        raise ValueError('%s: %d flags, expected %d' % (name, t.numel(), n))
+    return t
+
+
+def _check_axpby(op, A, X, d, outs, beta, Z, zflags=None):
+    """Operands of alpha * (A @ X) + beta * Z: every (tensor, name) of `outs` is [n_rows, d] and not X, Z is [n_rows, d] when beta != 0, zflags
+    holds one byte per row.  Returns Z's pointer for the call: None when beta == 0 (Z is then not read)."""
+    for t, nm in outs:
+        if _check_xy(A, t, nm) != d or t.data_ptr() == X.data_ptr():
+            raise ValueError('%s: %s must be [n_rows, d] and must not alias X' % (op, nm))
+    if beta != 0.0 and (Z is None or _check_xy(A, Z, 'Z') != d):
+        raise ValueError('%s: Z [n_rows, d] required when beta != 0' % op)
+    if zflags is not None:
+        _check_flags(zflags, A.n_rows, 'zflags')
+    return _ptr(Z) if beta != 0.0 else None
+
+
+def _check_rows(idx, n, name, check_range=True):
+    """Host-side bounds check of a device index list against n rows (two small reads); hot loops validate once and pass check_range=False."""
+    if check_range and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+        raise IndexError('%s: index out of range' % name)
+
+
 def spmm(A, X, alpha=1.0, beta=0.0, Z=None, out=None, row_scale=None, rows_from=0):
     """out = alpha * (A @ X) + beta * Z.   X: [A.n_cols, d]; out, Z: [A.n_rows, d].   row_scale [n_rows] (optional): the product's rows are
     multiplied by it in the epilogue, out = alpha * diag(row_scale) (A @ X) + beta * Z.   rows_from (optional hint): output rows below it
     are not needed and MAY be left unwritten (a blocked plan skips the launches that only produce them)."""
     d = _check_xy(A, X, 'X', A.n_cols)
     Y = torch.empty(A.n_rows, d, dtype=torch.float32, device=X.device) if out is None else out
-    if _check_xy(A, Y, 'out') != d or Y.data_ptr() == X.data_ptr():
-        raise ValueError('spmm: out must be [n_rows, d] and must not alias X')
-    if beta != 0.0:
-        if Z is None or _check_xy(A, Z, 'Z') != d:
-            raise ValueError('spmm: Z [n_rows, d] required when beta != 0')
-    L, zp, st = _lib.lib(), (_ptr(Z) if beta != 0.0 else None), _stream()
-    tok = EVENT_HOOK.begin('axpby') if EVENT_HOOK is not None else None
+    zp = _check_axpby('spmm', A, X, d, ((Y, 'out'),), beta, Z)
+    L, st = _lib.lib(), _stream()
     if row_scale is not None:
         _dev(row_scale, torch.float32, 'row_scale', 1)
         if row_scale.numel() != A.n_rows:
             raise ValueError('spmm: row_scale needs one entry per output row')
         _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_rscale_f32(p, _ptr(X), d, _ptr(row_scale), alpha, beta, zp, _ptr(Y), st), 'arl_spmm_blocked_rscale_f32'),
                        lambda p: check(L.arl_spmm_csr_rscale_f32(p, _ptr(X), d, _ptr(row_scale), alpha, beta, zp, _ptr(Y), st), 'arl_spmm_csr_rscale_f32'),
-                       rows_from=rows_from)
+                       'axpby', rows_from=rows_from)
     else:
         _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_f32(p, _ptr(X), d, alpha, beta, zp, None, _ptr(Y), st), 'arl_spmm_blocked_f32'),
-                       lambda p: check(L.arl_spmm_csr_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(Y), st), 'arl_spmm_csr_f32'), rows_from=rows_from)
-    if tok is not None:
-        EVENT_HOOK.end(tok)
+                       lambda p: check(L.arl_spmm_csr_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(Y), st), 'arl_spmm_csr_f32'), 'axpby', rows_from=rows_from)
     return Y
 
 
@@ -678,41 +701,21 @@ def spmm_layersum(A, X, S_in, S, Y=None):
     if S.data_ptr() == X.data_ptr():
         raise ValueError('spmm_layersum: S must not alias X')
     L, st = _lib.lib(), _stream()
-    tok = EVENT_HOOK.begin('layersum') if EVENT_HOOK is not None else None
     _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_layersum_f32(p, _ptr(X), d, _ptr(S_in), _ptr(S), _ptr(Y), st), 'arl_spmm_blocked_layersum_f32'),
-                   lambda p: check(L.arl_spmm_csr_layersum_f32(p, _ptr(X), d, _ptr(S_in), _ptr(S), _ptr(Y), st), 'arl_spmm_csr_layersum_f32'))
-    if tok is not None:
-        EVENT_HOOK.end(tok)
+                   lambda p: check(L.arl_spmm_csr_layersum_f32(p, _ptr(X), d, _ptr(S_in), _ptr(S), _ptr(Y), st), 'arl_spmm_csr_layersum_f32'), 'layersum')
     return S
-
-
-def _check_flags(t, n, name):
-    _dev(t, torch.uint8, name, 1)
-    if t.numel() != n:
-        raise ValueError('%s: %d flags, expected %d' % (name, t.numel(), n))
-    return t
 
 
 def spmm_adam(A, X, alpha, beta, Z, P, M, V, lr, step, betas=(0.9, 0.999), eps=1e-8, zflags=None):
     """g = alpha*(A@X) + beta*Z ; Adam update of (P, M, V) with g, fused in the SpMM epilogue.  X: [A.n_cols, d]; rest [A.n_rows, d].
     zflags (uint8 [n_rows], optional): Z is read only on flagged rows (it is zero elsewhere)."""
     d = _check_xy(A, X, 'X', A.n_cols)
-    for t, nm in ((P, 'P'), (M, 'M'), (V, 'V')):
-        if _check_xy(A, t, nm) != d or t.data_ptr() == X.data_ptr():
-            raise ValueError('spmm_adam: %s shape/alias error' % nm)
-    if beta != 0.0:
-        if Z is None or _check_xy(A, Z, 'Z') != d:
-            raise ValueError('spmm_adam: Z shape mismatch')
-    if zflags is not None:
-        _check_flags(zflags, A.n_rows, 'zflags')
-    L, zp, st = _lib.lib(), (_ptr(Z) if beta != 0.0 else None), _stream()
-    tok = EVENT_HOOK.begin('adam') if EVENT_HOOK is not None else None
+    zp = _check_axpby('spmm_adam', A, X, d, ((P, 'P'), (M, 'M'), (V, 'V')), beta, Z, zflags)
+    L, st = _lib.lib(), _stream()
     _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_adam_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(zflags), _ptr(P), _ptr(M), _ptr(V), lr, betas[0],
                                                                      betas[1], eps, int(step), st), 'arl_spmm_blocked_adam_f32'),
                    lambda p: check(L.arl_spmm_csr_adam_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(zflags), _ptr(P), _ptr(M), _ptr(V), lr, betas[0], betas[1], eps,
-                                                           int(step), st), 'arl_spmm_csr_adam_f32'))
-    if tok is not None:
-        EVENT_HOOK.end(tok)
+                                                           int(step), st), 'arl_spmm_csr_adam_f32'), 'adam')
 
 
 def spmm_flagged(A, X, xflags=None, alpha=1.0, beta=0.0, Z=None, zflags=None, out=None):
@@ -720,26 +723,18 @@ def spmm_flagged(A, X, xflags=None, alpha=1.0, beta=0.0, Z=None, zflags=None, ou
     mark_bits_) and Z is read only where the byte flag zflags != 0.  Either may be None (= dense)."""
     d = _check_xy(A, X, 'X', A.n_cols)
     Y = torch.empty(A.n_rows, d, dtype=torch.float32, device=X.device) if out is None else out
-    if _check_xy(A, Y, 'out') != d or Y.data_ptr() == X.data_ptr():
-        raise ValueError('spmm_flagged: out must be [n_rows, d] and must not alias X')
-    if beta != 0.0 and (Z is None or _check_xy(A, Z, 'Z') != d):
-        raise ValueError('spmm_flagged: Z [n_rows, d] required when beta != 0')
+    zp = _check_axpby('spmm_flagged', A, X, d, ((Y, 'out'),), beta, Z, zflags)
     if xflags is not None:          # bitmap: int32 words, bit c&31 of word c>>5
         _dev(xflags, torch.int32, 'xflags (bitmap)', 1)
         if xflags.numel() != (A.n_cols + 31) // 32:
             raise ValueError('spmm_flagged: bitmap needs ceil(n_cols/32) int32 words')
-    if zflags is not None:
-        _check_flags(zflags, A.n_rows, 'zflags')
-    L, zp, st = _lib.lib(), (_ptr(Z) if beta != 0.0 else None), _stream()
-    tok = EVENT_HOOK.begin('masked' if xflags is not None else 'axpby') if EVENT_HOOK is not None else None
+    L, st = _lib.lib(), _stream()
     csr = lambda p: check(L.arl_spmm_csr_flagged_f32(p, _ptr(X), d, _ptr(xflags), alpha, beta, zp, _ptr(zflags), _ptr(Y), st), 'arl_spmm_csr_flagged_f32')
     if xflags is not None:              # the masked hop skips most edges: the blocked record stream with a bit test per record, else the row-per-group kernel
         _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_flagged_f32(p, _ptr(X), d, _ptr(xflags), alpha, beta, zp, _ptr(zflags), _ptr(Y), st),
-                                             'arl_spmm_blocked_flagged_f32'), csr)
+                                             'arl_spmm_blocked_flagged_f32'), csr, 'masked')
     else:
-        _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(zflags), _ptr(Y), st), 'arl_spmm_blocked_f32'), csr)
-    if tok is not None:
-        EVENT_HOOK.end(tok)
+        _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(zflags), _ptr(Y), st), 'arl_spmm_blocked_f32'), csr, 'axpby')
     return Y
 
 
@@ -764,8 +759,7 @@ def spmm_rows(A, X, rows, layers=(), alpha=1.0, nsplit=ROWS_NSPLIT, out=None, wo
     d = _check_xy(A, X, 'X', A.n_cols)
     _dev(rows, torch.int32, 'rows', 1)
     n = rows.numel()
-    if check_range and n and (int(rows.min()) < 0 or int(rows.max()) >= A.n_rows):
-        raise IndexError('spmm_rows: row index out of range')
+    _check_rows(rows, A.n_rows, 'spmm_rows', check_range)
     if len(layers) > 8:
         raise ValueError('spmm_rows: at most 8 layer tables')
     for t in layers:
@@ -797,8 +791,7 @@ def spmm_rows(A, X, rows, layers=(), alpha=1.0, nsplit=ROWS_NSPLIT, out=None, wo
 
 def mark_rows_(flags, idx, value, check_range=True):
     _dev(flags, torch.uint8, 'flags', 1); _dev(idx, torch.int32, 'idx', 1)
-    if check_range and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= flags.numel()):
-        raise IndexError('mark_rows_: index out of range')
+    _check_rows(idx, flags.numel(), 'mark_rows_', check_range)
     check(_lib.lib().arl_mark_rows_u8(_ptr(flags), _ptr(idx), idx.numel(), int(value), _stream()), 'arl_mark_rows_u8')
     return flags
 
@@ -812,8 +805,7 @@ def batch_rows_set_(G, flags, bits, idx, src, scale=1.0, check_range=True, row_s
     N, d = G.shape
     if flags.numel() != N or bits.numel() != (N + 31) // 32 or src.shape != (idx.numel(), d):
         raise ValueError('batch_rows_set_: shape mismatch')
-    if check_range and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= N):
-        raise IndexError('batch_rows_set_: index out of range')
+    _check_rows(idx, N, 'batch_rows_set_', check_range)
     if row_scale is not None and _dev(row_scale, torch.float32, 'row_scale', 1).numel() != idx.numel():
         raise ValueError('batch_rows_set_: row_scale must have one entry per index')
     if dup_bits is not None and _dev(dup_bits, torch.int32, 'dup_bits', 1).numel() != bits.numel():
@@ -828,8 +820,7 @@ def batch_rows_clear_(G, flags, bits, idx, check_range=True, dup_bits=None):
     N, d = G.shape
     if flags.numel() != N or bits.numel() != (N + 31) // 32:
         raise ValueError('batch_rows_clear_: shape mismatch')
-    if check_range and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= N):
-        raise IndexError('batch_rows_clear_: index out of range')
+    _check_rows(idx, N, 'batch_rows_clear_', check_range)
     if dup_bits is not None and _dev(dup_bits, torch.int32, 'dup_bits', 1).numel() != bits.numel():
         raise ValueError('batch_rows_clear_: dup_bits must have the size of bits')
     check(_lib.lib().arl_batch_rows_clear_f32(_ptr(G), _ptr(flags), _ptr(bits), _ptr(idx), idx.numel(), d, _ptr(dup_bits), _stream()), 'arl_batch_rows_clear_f32')
@@ -839,16 +830,14 @@ def mark_bits_(bits, idx, set_, n_nodes, check_range=True):
     _dev(bits, torch.int32, 'bits', 1); _dev(idx, torch.int32, 'idx', 1)
     if bits.numel() != (n_nodes + 31) // 32:
         raise ValueError('mark_bits_: bitmap size')
-    if check_range and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_nodes):
-        raise IndexError('mark_bits_: index out of range')
+    _check_rows(idx, n_nodes, 'mark_bits_', check_range)
     check(_lib.lib().arl_mark_rows_bits_u32(_ptr(bits), _ptr(idx), idx.numel(), 1 if set_ else 0, _stream()), 'arl_mark_rows_bits_u32')
     return bits
 
 
 def zero_rows_(dst, idx, check_range=True):
     _dev(dst, torch.float32, 'dst', 2); _dev(idx, torch.int32, 'idx', 1)
-    if check_range and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= dst.shape[0]):
-        raise IndexError('zero_rows_: index out of range')
+    _check_rows(idx, dst.shape[0], 'zero_rows_', check_range)
     check(_lib.lib().arl_zero_rows_f32(_ptr(dst), _ptr(idx), idx.numel(), dst.shape[1], _stream()), 'arl_zero_rows_f32')
     return dst
 
@@ -907,8 +896,7 @@ def sgd_dense(p, g, lr):
 
 def gather_rows(src, idx, check_range=True):
     _dev(src, torch.float32, 'src', 2); _dev(idx, torch.int32, 'idx', 1)
-    if check_range and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= src.shape[0]):
-        raise IndexError('gather_rows: index out of range')
+    _check_rows(idx, src.shape[0], 'gather_rows', check_range)
     dst = torch.empty(idx.numel(), src.shape[1], dtype=torch.float32, device=src.device)
     check(_lib.lib().arl_gather_rows_f32(_ptr(src), _ptr(idx), idx.numel(), src.shape[1], _ptr(dst), _stream()), 'arl_gather_rows_f32')
     return dst
@@ -918,8 +906,7 @@ def scatter_add_rows(dst, idx, src, scale=1.0, check_range=True):
     _dev(dst, torch.float32, 'dst', 2); _dev(src, torch.float32, 'src', 2); _dev(idx, torch.int32, 'idx', 1)
     if src.shape != (idx.numel(), dst.shape[1]):
         raise ValueError('scatter_add_rows: shape mismatch')
-    if check_range and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= dst.shape[0]):
-        raise IndexError('scatter_add_rows: index out of range')
+    _check_rows(idx, dst.shape[0], 'scatter_add_rows', check_range)
     check(_lib.lib().arl_scatter_add_rows_f32(_ptr(dst), _ptr(idx), idx.numel(), dst.shape[1], _ptr(src), scale, _stream()), 'arl_scatter_add_rows_f32')
     return dst
 
@@ -930,8 +917,7 @@ def rows_axpy_unique_(dst, src, idx, alpha=1.0, check_range=True, dup_bits=None)
     _dev(dst, torch.float32, 'dst', 2); _dev(src, torch.float32, 'src', 2); _dev(idx, torch.int32, 'idx', 1)
     if src.shape != dst.shape or src.data_ptr() == dst.data_ptr():
         raise ValueError('rows_axpy_unique_: dst and src must be distinct tables of one shape')
-    if check_range and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= dst.shape[0]):
-        raise IndexError('rows_axpy_unique_: index out of range')
+    _check_rows(idx, dst.shape[0], 'rows_axpy_unique_', check_range)
     check(_lib.lib().arl_rows_axpy_unique_f32(_ptr(dst), _ptr(src), _ptr(idx), idx.numel(), dst.shape[1], float(alpha), _ptr(dup_bits), _stream()), 'arl_rows_axpy_unique_f32')
     return dst
 
@@ -1179,8 +1165,7 @@ def sddmm_rows_dense(dY, X, rows, col_off, n_cols, out=None):
     if dY.shape[1] != X.shape[1] or col_off < 0 or col_off + n_cols > X.shape[0]:
         raise ValueError('sddmm_rows_dense: shape mismatch')
     _check_width(X.shape[1], 'sddmm_rows_dense', multiple_of_4=False)
-    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= dY.shape[0]):
-        raise IndexError('sddmm_rows_dense: row out of range')
+    _check_rows(rows, dY.shape[0], 'sddmm_rows_dense')
     if out is None:
         out = torch.zeros(rows.numel(), n_cols, dtype=torch.float32, device=X.device)
     else:
@@ -1579,8 +1564,7 @@ def _ncf_rows(rows, N, check_range):
     if rows is None:
         return None
     _dev(rows, torch.int32, 'rows', 1)
-    if check_range and rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= N):
-        raise IndexError('ncf_tower: row index out of range')
+    _check_rows(rows, N, 'ncf_tower', check_range)
     return rows
 
 
@@ -1687,158 +1671,6 @@ def bpr_l2_backward(emb, item_off, u, p, n, reg, norms4, G, workspace, upstream=
     check(_lib.lib().arl_bpr_l2_backward_f32(_ptr(emb), emb.shape[1], item_off, _ptr(u), _ptr(p), _ptr(n), B, reg, upstream, _ptr(norms4), _ptr(G),
                                              _ptr(workspace), _stream()), 'arl_bpr_l2_backward_f32')
     return G
-
-
-# ------------------------------------------------------------------------------------------------ L2-blocked SpMM plan
-class TiledPlan:
-    """Schedule of the L2-blocked SpMM (include/arlib_amd.h: arl_tiled) for a CSRGraph.
-
-    row_groups: list of (lo, hi) row ranges binned separately (for the bipartite adjacency: [(0, U), (U, N)], so that a bin's
-    rows all gather from the same table and every sweep is homogeneous).  Rows are sorted by degree and dealt snake-wise into
-    bins of <= cap rows, which gives every bin (nearly) the same number of edges; the hottest rows land in different bins.
-    Built with torch ops on the graph's device (one stable sort of the edge list)."""
-
-    def __init__(self, A, row_groups=None, cap=384, col_block=16384, n_slots=256, d=64, hub_threshold=1024):
-        dev = A.device
-        lpr = 4 if d <= 16 else 8 if d <= 32 else 16 if d <= 64 else 32 if d <= 128 else 64
-        self.n_groups = 16 * (64 // lpr)                          # lane groups per 1024-thread workgroup
-        N = A.n_rows
-        rp = A.rowptr.to(torch.int64)
-        deg = (rp[1:] - rp[:-1])
-        if row_groups is None:
-            row_groups = [(0, N)]
-        if cap > 65535 or cap < 1:
-            raise ValueError('cap must be in [1, 65535]')
-        bin_of_row = torch.full((N,), -1, dtype=torch.int64, device=dev)
-        rloc = torch.zeros(N, dtype=torch.int64, device=dev)
-        self.hub_threshold = int(hub_threshold)
-        bins = 0
-        covered = 0
-        for lo, hi in row_groups:
-            covered += hi - lo
-            # rows longer than hub_threshold are left to the chunked CSR kernel (one lane group owning a 100k-edge row would
-            # serialise the whole sweep); they are few and carry a small share of the edges
-            order = torch.sort(deg[lo:hi], descending=True, stable=True)[1] + lo
-            order = order[deg[order] <= self.hub_threshold]
-            n = order.numel()
-            if n <= 0:
-                continue
-            nb = -(-n // cap)
-            nb = -(-nb // n_slots) * n_slots                      # whole sweeps
-            k = torch.arange(n, device=dev)
-            cyc, pos = k // nb, k % nb
-            b = torch.where(cyc % 2 == 0, pos, nb - 1 - pos)
-            bin_of_row[order] = bins + b
-            rloc[order] = cyc
-            bins += nb
-        if covered != N:
-            raise ValueError('row_groups must cover every row exactly once')
-        self.n_slots, self.cap, self.col_block = int(n_slots), int(cap), int(col_block)
-        self.n_sweeps = bins // n_slots
-        self.n_cb = -(-A.n_cols // col_block)
-        self.n_rows, self.n_cols, self.nnz, self.device = N, A.n_cols, A.nnz, dev
-        self._A = A
-        binned = bin_of_row >= 0
-        self.hub_rows = (~binned).nonzero().squeeze(1)             # handled by the chunked CSR kernel
-        bin_rows = torch.full((bins, cap), -1, dtype=torch.int32, device=dev)
-        bin_rows[bin_of_row[binned], rloc[binned]] = torch.arange(N, dtype=torch.int32, device=dev)[binned]
-        self.bin_rows = bin_rows.contiguous()
-        # owner group of a local row: snake over the groups (local rows are in descending-degree order inside a bin)
-        ng = self.n_groups
-        owner = torch.where((rloc // ng) % 2 == 0, rloc % ng, ng - 1 - rloc % ng)
-        row_e = torch.repeat_interleave(torch.arange(N, device=dev), deg)
-        keep = binned[row_e]
-        e_idx = keep.nonzero().squeeze(1)                          # CSR positions of the edges of binned rows
-        row_e = row_e[e_idx]
-        seg = bin_of_row[row_e] * ng + owner[row_e]                          # one contiguous edge list per (bin, owner group)
-        key = (seg * self.n_cb + (A.col[e_idx].to(torch.int64) // col_block)) * cap + rloc[row_e]
-        order = e_idx[torch.sort(key, stable=True)[1]]
-        self.order = order.to(torch.int32) if A.nnz < 2 ** 31 else order
-        self.e_col = A.col[order].contiguous()
-        self.e_val = A.val[order].contiguous()
-        self.e_row = rloc[torch.repeat_interleave(torch.arange(N, device=dev), deg)[order]].to(torch.int16).contiguous()
-        self.nnz_binned = int(order.numel())
-        # hub pass: the graph's chunk plan restricted to the hub rows, row tasks disabled (n_rows = 0)
-        self.hub_graph = A.chunks_only(self.hub_rows) if self.hub_rows.numel() else None
-        counts = torch.bincount(seg, minlength=bins * self.n_groups)
-        flat = torch.zeros(bins * self.n_groups + 1, dtype=torch.int64, device=dev)
-        flat[1:] = torch.cumsum(counts, 0)
-        self.seg_ptr = flat.to(torch.int32).contiguous()
-        self.group_edges_max, self.group_edges_mean = int(counts.max()), float(counts.float().mean())
-        idx = None
-        del row_e, seg, key, counts, flat, idx
-
-    def update_values(self, val):
-        """New edge values in CSR order (same pattern)."""
-        _dev(val, torch.float32, 'val', 1)
-        if val.numel() != self.nnz:
-            raise ValueError('update_values: wrong length')
-        self.e_val = val[self.order.long()].contiguous()
-        if self.hub_graph is not None:
-            self.hub_graph.val = val
-
-    def _struct(self):
-        t = _lib.arl_tiled()
-        t.n_sweeps, t.n_slots, t.cap, t.n_cb, t.nnz = self.n_sweeps, self.n_slots, self.cap, self.n_cb, self.nnz_binned
-        t.n_groups = self.n_groups
-        t.bin_rows, t.seg_ptr = self.bin_rows.data_ptr(), self.seg_ptr.data_ptr()
-        t.e_col, t.e_val, t.e_row = self.e_col.data_ptr(), self.e_val.data_ptr(), self.e_row.data_ptr()
-        return t
-
-
-def _check_tiled(P, X, name, rows):
-    _dev(X, torch.float32, name, 2)
-    if X.shape[0] != rows:
-        raise ValueError('%s: %d rows, expected %d' % (name, X.shape[0], rows))
-    if X.device != P.device:
-        raise ValueError('%s on %s, plan on %s' % (name, X.device, P.device))
-    d = X.shape[1]
-    if d % 4 or d > 256 or P.cap * (d + 4) * 4 > 160 * 1024:
-        raise ValueError('embedding size %d does not fit the plan (cap %d rows of LDS accumulators)' % (d, P.cap))
-    return d
-
-
-def spmm_tiled(P, X, alpha=1.0, beta=0.0, Z=None, zflags=None, out=None):
-    """out = alpha*(A@X) + beta*Z through the L2-blocked schedule `P` (same numbers as spmm up to fp32 summation order)."""
-    d = _check_tiled(P, X, 'X', P.n_cols)
-    Y = torch.empty(P.n_rows, d, dtype=torch.float32, device=X.device) if out is None else out
-    if _check_tiled(P, Y, 'out', P.n_rows) != d or Y.data_ptr() == X.data_ptr():
-        raise ValueError('spmm_tiled: out must be [n_rows, d] and must not alias X')
-    if beta != 0.0 and (Z is None or _check_tiled(P, Z, 'Z', P.n_rows) != d):
-        raise ValueError('spmm_tiled: Z [n_rows, d] required when beta != 0')
-    if zflags is not None:
-        _check_flags(zflags, P.n_rows, 'zflags')
-    t = P._struct()
-    tok = EVENT_HOOK.begin('axpby') if EVENT_HOOK is not None else None
-    check(_lib.lib().arl_spmm_tiled_f32(C.byref(t), _ptr(X), d, alpha, beta, _ptr(Z) if beta != 0.0 else None, _ptr(zflags), _ptr(Y), _stream()), 'arl_spmm_tiled_f32')
-    if P.hub_graph is not None:          # the few rows longer than hub_threshold: chunked CSR kernel, same epilogue
-        s = P.hub_graph._struct(d)
-        check(_lib.lib().arl_spmm_csr_flagged_f32(C.byref(s), _ptr(X), d, None, alpha, beta, _ptr(Z) if beta != 0.0 else None, _ptr(zflags), _ptr(Y), _stream()),
-              'arl_spmm_csr_flagged_f32 (hub rows)')
-    if tok is not None:
-        EVENT_HOOK.end(tok)
-    return Y
-
-
-def spmm_tiled_adam(P, X, alpha, beta, Z, Pm, M, V, lr, step, betas=(0.9, 0.999), eps=1e-8, zflags=None):
-    d = _check_tiled(P, X, 'X', P.n_cols)
-    for t_, nm in ((Pm, 'P'), (M, 'M'), (V, 'V')):
-        if _check_tiled(P, t_, nm, P.n_rows) != d or t_.data_ptr() == X.data_ptr():
-            raise ValueError('spmm_tiled_adam: %s shape/alias error' % nm)
-    if beta != 0.0 and (Z is None or _check_tiled(P, Z, 'Z', P.n_rows) != d):
-        raise ValueError('spmm_tiled_adam: Z shape mismatch')
-    if zflags is not None:
-        _check_flags(zflags, P.n_rows, 'zflags')
-    t = P._struct()
-    tok = EVENT_HOOK.begin('adam') if EVENT_HOOK is not None else None
-    check(_lib.lib().arl_spmm_tiled_adam_f32(C.byref(t), _ptr(X), d, alpha, beta, _ptr(Z) if beta != 0.0 else None, _ptr(zflags), _ptr(Pm), _ptr(M), _ptr(V),
-                                             lr, betas[0], betas[1], eps, int(step), _stream()), 'arl_spmm_tiled_adam_f32')
-    if P.hub_graph is not None:
-        s = P.hub_graph._struct(d)
-        check(_lib.lib().arl_spmm_csr_adam_f32(C.byref(s), _ptr(X), d, alpha, beta, _ptr(Z) if beta != 0.0 else None, _ptr(zflags), _ptr(Pm), _ptr(M), _ptr(V),
-                                               lr, betas[0], betas[1], eps, int(step), _stream()), 'arl_spmm_csr_adam_f32 (hub rows)')
-    if tok is not None:
-        EVENT_HOOK.end(tok)
 
 
 # ================================================================================================ AUSH's GAN (arl_gan_*, csrc/arl_gan.hip)
@@ -1993,8 +1825,7 @@ def gan_template(user_set, ui_rowptr, ui_col, ui_val, pos, items, mask=None, ite
     _gan_csr(ui_rowptr, ui_col, ui_val, U, I, 'gan_template interactions')
     if F > U or S > I:
         raise ValueError('gan_template: F <= U and S <= I needed (row r and position j are read as a user and an item)')
-    if F and (int(user_set.min()) < 0 or int(user_set.max()) >= U):
-        raise IndexError('gan_template: user id out of range')
+    _check_rows(user_set, U, 'gan_template: user id')
     if int(pos.min()) < -1 or int(pos.max()) >= S or int(items.min()) < 0 or int(items.max()) >= I:
         raise IndexError('gan_template: pos / items out of range')
     if mask is not None:
@@ -2041,8 +1872,7 @@ def gan_hash_mask(F, items, item_p, seed=0, call=0):
     _dev(items, torch.int32, 'items', 1); _dev(item_p, torch.float32, 'item_p', 1)
     S = items.numel()
     _gan_template_size(F, S, 'gan_hash_mask')
-    if S and (int(items.min()) < 0 or int(items.max()) >= item_p.numel()):
-        raise IndexError('gan_hash_mask: items out of range')
+    _check_rows(items, item_p.numel(), 'gan_hash_mask: items')
     out = torch.empty(int(F), S, dtype=torch.uint8, device=items.device)
     check(_lib.lib().arl_gan_hash_mask_u8(int(F), S, _ptr(items), _ptr(item_p), int(seed) & (2 ** 64 - 1), int(call) & (2 ** 64 - 1), _ptr(out), _stream()),
           'arl_gan_hash_mask_u8')

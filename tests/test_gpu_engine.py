@@ -207,38 +207,6 @@ def test_spmm_rows_and_flagged_primitives(mods, d):
     assert float(Z.abs().max()) == 0.0
 
 
-def test_tiled_l2_blocked_spmm_matches_row_kernel(mods):
-    """The L2-blocked schedule (TiledPlan: LDS-resident accumulators per bin, group-owned rows, hub rows on the chunked kernel)
-    must give the same numbers as the row-per-wave kernel for every epilogue, incl. rows longer than the hub threshold."""
-    ops, engine = mods
-    rng = np.random.default_rng(12)
-    U, I, d = 9000, 1200, 64
-    us = np.repeat(np.arange(U), 9)
-    its = np.floor(I * rng.random(len(us)) ** 2).astype(np.int64)
-    key = np.unique(us * I + its)
-    us, its = (key // I).astype(np.int32), (key % I).astype(np.int32)
-    rowptr, col, w = O.bipartite_csr(us, its, U, I)
-    val = O.norm_adj_values(rowptr, col, w)
-    A = ops.CSRGraph(rowptr, col, val, DEV)
-    N = U + I
-    P = ops.TiledPlan(A, [(0, U), (U, N)], cap=384, col_block=2048, hub_threshold=600)
-    assert P.hub_rows.numel() > 0 and np.diff(rowptr).max() > 600
-    X = torch.randn(N, d, device=DEV); Z = torch.randn(N, d, device=DEV)
-    ref = ops.spmm(A, X, 0.5, 0.25, Z)
-    got = ops.spmm_tiled(P, X, 0.5, 0.25, Z)
-    assert rel_err(got.cpu().numpy(), ref.cpu().numpy()) < 1e-5
-    assert torch.equal(got, ops.spmm_tiled(P, X, 0.5, 0.25, Z))                      # deterministic (no atomics)
-    p1, m1, v1 = (torch.randn(N, d, device=DEV) * 0.1 for _ in range(3)); v1 = v1.abs()
-    p2, m2, v2 = p1.clone(), m1.clone(), v1.clone()
-    ops.spmm_adam(A, X, 0.25, 0.25, Z, p1, m1, v1, 0.005, 3)
-    ops.spmm_tiled_adam(P, X, 0.25, 0.25, Z, p2, m2, v2, 0.005, 3)
-    assert rel_err(p2.cpu().numpy(), p1.cpu().numpy()) < 1e-5 and rel_err(v2.cpu().numpy(), v1.cpu().numpy()) < 1e-5
-    val2 = val * 0.5
-    P.update_values(T(val2))
-    ref2 = ops.spmm(A.with_values(T(val2)), X)
-    assert rel_err(ops.spmm_tiled(P, X).cpu().numpy(), ref2.cpu().numpy()) < 1e-5
-
-
 def test_simgcl_fused_step_matches_reference(mods, ml100k):
     """Fused SimGCL step (shared first hop, row-subset last hops, ONE backward pass for the three forwards) against the
     reference's step with the same injected noise: losses, and tables after the Adam update."""

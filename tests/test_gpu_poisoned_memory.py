@@ -925,28 +925,6 @@ def _(ops):
     return run, ref
 
 
-@case('spmm_tiled')
-def _(ops):
-    g = graph(ops)
-    Pl = ops.TiledPlan(g.A, [(0, g.U), (g.U, g.N)], cap=48, col_block=64, hub_threshold=100)
-    assert Pl.hub_rows.numel() > 0
-    X, Z, st, zf = spmm_inputs(g, 64, 106)
-
-    def run(caller):
-        Pm, M, V = (t.clone() for t in st)
-        ops.spmm_tiled_adam(Pl, X, 0.25, 0.5, Z * zf[:, None], Pm, M, V, 0.005, 7, zflags=zf)
-        return {'y': ops.spmm_tiled(Pl, X, 0.5, 0.25, Z, out=Pz(g.N, 64) if caller else None), 'P': Pm, 'M': M, 'V': V}
-
-    def ref():
-        grad = 0.25 * (g.M @ X.double()) + 0.5 * Z.double() * zf.double()[:, None]
-        Pm, M, V = adam64(st[0].double(), grad, st[1].double(), st[2].double(), 0.005, 7)
-        return {'y': 0.5 * (g.M @ X.double()) + 0.25 * Z.double(), 'P': Pm, 'M': M, 'V': V}
-    return run, ref
-
-
-CASES['spmm_tiled_adam'] = CASES['spmm_tiled']
-
-
 # GAN ops: M, N, K straddling the 128 x 128 x 16 tile of the gemm, F and S ragged against the 64-row / 256-column blocks of the row kernels
 @case('gan_gemm')
 def _(ops):

@@ -193,30 +193,7 @@ def test_spmm_adam_epilogue(ops, d, use_zflags):
     check_adam(Pt, Mt, Vt, P0, M0, V0, g, 0.005, 7)
 
 
-# ------------------------------------------------------------------------------------------------ SpMM, tiled and blocked schedules
-@pytest.mark.parametrize('d', WIDTHS)
-def test_spmm_tiled_schedule(ops, d):
-    U, I, rowptr, col, val = bipartite(d + 4, U=500, I=120, hot=3, hot_deg=300)
-    N = U + I
-    A, A64 = graph(ops, rowptr, col, val), sp64(rowptr, col, val)
-    cap = min(64, (160 * 1024) // ((d + 4) * 4))
-    plan = ops.TiledPlan(A, row_groups=[(0, U), (U, N)], cap=cap, col_block=128, n_slots=4, d=d, hub_threshold=100)
-    assert plan.hub_graph is not None and plan.n_sweeps > 0          # both the binned sweep and the hub pass run
-    rng = np.random.default_rng(500 + d)
-    X = rng.standard_normal((N, d)).astype(np.float32)
-    Z = rng.standard_normal((N, d)).astype(np.float32)
-    zf = (rng.random(N) < 0.3).astype(np.uint8)
-    Zs = Z * zf[:, None]
-    AX = A64 @ X.astype(np.float64)
-    assert close(H(ops.spmm_tiled(plan, T(X))), AX, tol=TOL)
-    assert close(H(ops.spmm_tiled(plan, T(X), 0.5, -2.0, T(Z))), 0.5 * AX - 2.0 * Z, tol=TOL)
-    assert close(H(ops.spmm_tiled(plan, T(X), 0.5, 2.0, T(Zs), T(zf))), 0.5 * AX + 2.0 * Zs, tol=TOL)
-    P0, M0, V0 = adam_state(rng, N, d)
-    Pt, Mt, Vt = T(P0), T(M0), T(V0)
-    ops.spmm_tiled_adam(plan, T(X), 0.25, 0.5, T(Zs), Pt, Mt, Vt, 0.005, 3, zflags=T(zf))
-    check_adam(Pt, Mt, Vt, P0, M0, V0, 0.25 * AX + 0.5 * Zs, 0.005, 3)
-
-
+# ------------------------------------------------------------------------------------------------ SpMM, blocked schedule
 @pytest.mark.parametrize('d', WIDTHS)
 def test_spmm_blocked_schedule_or_csr_fallback(ops, d, monkeypatch):
     """A graph with a register-blocked plan: d = 64 and 128 run through it, every other width keeps the CSR kernel; the numbers hold both ways."""
@@ -607,26 +584,6 @@ def test_spmm_family_rejects_width(ops, d):
     assert L.arl_sddmm_csr_f32(P(A.rowptr), P(A.col), N, d, P(Yw), P(Xw), 1.0, P(gval), st) == ARL_E_DIM
     torch.cuda.synchronize()
     assert float(Yw.abs().max()) == 0.0 and float(gval.abs().max()) == 0.0         # nothing launched
-
-
-@pytest.mark.parametrize('d', (6, 260))
-def test_tiled_schedule_rejects_width(ops, d):
-    U, I, rowptr, col, val = bipartite(8, U=500, I=120, hot=3, hot_deg=300)
-    N = U + I
-    A = graph(ops, rowptr, col, val)
-    plan = ops.TiledPlan(A, row_groups=[(0, U), (U, N)], cap=64, col_block=128, n_slots=4, d=256, hub_threshold=100)
-    X = torch.zeros(N, d, device=DEV)
-    with pytest.raises(ValueError):
-        ops.spmm_tiled(plan, X)
-    with pytest.raises(ValueError):
-        ops.spmm_tiled_adam(plan, X, 1.0, 0.0, None, *(torch.zeros(N, d, device=DEV) for _ in range(3)), 0.01, 1)
-    L, st = _clib(), _stream()
-    Xw, Yw, Pw, Mw, Vw = (torch.zeros(N, 264, device=DEV) for _ in range(5))
-    t = plan._struct()
-    assert L.arl_spmm_tiled_f32(C.byref(t), P(Xw), d, 1.0, 0.0, None, None, P(Yw), st) == ARL_E_DIM
-    assert L.arl_spmm_tiled_adam_f32(C.byref(t), P(Xw), d, 1.0, 0.0, None, None, P(Pw), P(Mw), P(Vw), 0.01, 0.9, 0.999, 1e-8, 1, st) == ARL_E_DIM
-    torch.cuda.synchronize()
-    assert float(Yw.abs().max()) == 0.0
 
 
 @pytest.mark.parametrize('d', (6, 260))

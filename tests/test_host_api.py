@@ -333,11 +333,11 @@ def test_header_is_plain_c(tmp_path):
     subprocess.run(['gcc', '-x', 'c', '-std=c99', '-fsyntax-only', '-Wall', '-Werror', hdr], check=True)
     subprocess.run(['g++', '-x', 'c++', '-std=c++17', '-fsyntax-only', '-Wall', '-Werror', hdr], check=True)
     src = tmp_path / 'sz.c'
-    src.write_text('#include <stdio.h>\n#include "arlib_amd.h"\nint main(void) { printf("%zu %zu %zu\\n", sizeof(arl_csr), sizeof(arl_blocked), sizeof(arl_tiled)); return 0; }\n')
+    src.write_text('#include <stdio.h>\n#include "arlib_amd.h"\nint main(void) { printf("%zu %zu\\n", sizeof(arl_csr), sizeof(arl_blocked)); return 0; }\n')
     exe = tmp_path / 'sz'
     subprocess.run(['gcc', '-std=c99', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)], check=True)
     sizes = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert sizes == [ctypes.sizeof(_lib.arl_csr), ctypes.sizeof(_lib.arl_blocked), ctypes.sizeof(_lib.arl_tiled)]
+    assert sizes == [ctypes.sizeof(_lib.arl_csr), ctypes.sizeof(_lib.arl_blocked)]
 
 
 @pytest.mark.parametrize('rpw,hub,split,split_hubs', [(32, 40, True, True), (32, 40, True, False), (16, 100000, False, True), (32, 7, True, True), (32, 7, True, False),
@@ -534,3 +534,72 @@ def test_csrgraph_device_side_long_row_plan_equals_host_plan():
         assert torch.equal(g.chunk_begin[:nc], h.chunk_begin) and torch.equal(g.chunk_end[:nc], h.chunk_end)
         assert bool((g.chunk_begin[nc:] == g.chunk_end[nc:]).all())
         assert torch.equal(g.rowptr, h.rowptr)
+
+
+# The ten SpMM entries of the C ABI: (plan kind, arguments between `d` and `stream`, in call order).
+_SPMM_ENTRIES = {
+    'arl_spmm_csr_f32': ('csr', ('alpha', 'beta', 'Z', 'Y')),
+    'arl_spmm_csr_rscale_f32': ('csr', ('row_scale', 'alpha', 'beta', 'Z', 'Y')),
+    'arl_spmm_csr_flagged_f32': ('csr', ('xbits', 'alpha', 'beta', 'Z', 'zflags', 'Y')),
+    'arl_spmm_csr_layersum_f32': ('csr', ('S_in', 'S', 'Y')),
+    'arl_spmm_csr_adam_f32': ('csr', ('alpha', 'beta', 'Z', 'zflags', 'P', 'M', 'V', 'lr', 'beta1', 'beta2', 'eps', 'step')),
+    'arl_spmm_blocked_f32': ('blocked', ('alpha', 'beta', 'Z', 'zflags', 'Y')),
+    'arl_spmm_blocked_rscale_f32': ('blocked', ('row_scale', 'alpha', 'beta', 'Z', 'Y')),
+    'arl_spmm_blocked_flagged_f32': ('blocked', ('xbits', 'alpha', 'beta', 'Z', 'zflags', 'Y')),
+    'arl_spmm_blocked_layersum_f32': ('blocked', ('S_in', 'S', 'Y')),
+    'arl_spmm_blocked_adam_f32': ('blocked', ('alpha', 'beta', 'Z', 'zflags', 'P', 'M', 'V', 'lr', 'beta1', 'beta2', 'eps', 'step')),
+}
+_OK, _E_NULL, _E_DIM, _E_ARG = 0, -1, -2, -4
+
+
+def _spmm_refusal_table():
+    """(entry, defect label, {argument: value}, expected code): one valid call per entry and every single-defect call.  'X' as a value
+    means "the operand's own address" (aliasing); None is a NULL pointer."""
+    rows = []
+    for name, (kind, args) in _SPMM_ENTRIES.items():
+        rows.append((name, 'valid', {}, _OK))
+        out = 'P' if 'P' in args else 'Y'
+        required = [a for a in ('P', 'M', 'V', 'S_in', 'S') if a in args] or ['Y']
+        for a in required:
+            rows.append((name, 'NULL ' + a, {a: None}, _E_NULL))
+        if 'beta' in args:
+            rows.append((name, 'beta=0.5, NULL Z', {'beta': 0.5, 'Z': None}, _E_NULL))
+            rows.append((name, 'beta=0, NULL Z', {'beta': 0.0, 'Z': None}, _OK))
+        else:
+            rows.append((name, 'NULL Y is optional', {'Y': None}, _OK))
+        rows.append((name, out + ' aliases X', {out: 'X'}, _E_ARG))
+        if 'step' in args:
+            rows.append((name, 'step=0', {'step': 0}, _E_ARG))
+        if 'row_scale' in args:
+            rows.append((name, 'NULL row_scale', {'row_scale': None}, _E_NULL))
+        if 'xbits' in args:      # the CSR form takes NULL xbits as "no mask"; the blocked form refuses it
+            rows.append((name, 'NULL xbits', {'xbits': None}, _E_NULL if kind == 'blocked' else _OK))
+        rows.append((name, 'd=6', {'d': 6}, _E_DIM))
+        if kind == 'blocked':
+            rows.append((name, 'd=32', {'d': 32}, _E_DIM))
+    return rows
+
+
+def test_spmm_entries_refuse_single_defects():
+    """Every SpMM entry of the C ABI returns the documented ARL_E_* code for each single defect of its arguments and ARL_OK for a valid
+    call.  Every call is on an EMPTY plan (both launchers return ARL_OK for one after their argument checks, before any launch), the
+    operand pointers are host addresses the entries never dereference, the stream is NULL: no device is needed and nothing can launch."""
+    import ctypes as C
+    from arlib_amd import _lib
+    L = _lib.lib()
+    plans = {'csr': _lib.arl_csr(n_rows=0, nnz=0, n_chunks=0, n_long=0),
+             'blocked': _lib.arl_blocked(n_waves=0, rows_per_wave=32, loads_in_flight=32)}
+    ptr_names = ('X', 'Z', 'Y', 'P', 'M', 'V', 'S_in', 'S', 'zflags', 'xbits', 'row_scale')
+    bufs = {k: (C.c_float * 64)() for k in ptr_names}                        # distinct host arrays: no accidental aliasing
+    base = {k: C.addressof(b) for k, b in bufs.items()}
+    base.update(d=64, alpha=1.0, beta=0.5, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, step=1)
+    failures = []
+    for name, label, defect, want in _spmm_refusal_table():
+        kind, args = _SPMM_ENTRIES[name]
+        v = dict(base)
+        v.update({k: (base['X'] if x == 'X' else x) for k, x in defect.items()})
+        got = getattr(L, name)(C.byref(plans[kind]), v['X'], v['d'], *[v[a] for a in args], None)
+        if got != want:
+            failures.append((name, label, got, want))
+    assert not failures, failures
+    assert len(_spmm_refusal_table()) >= 10 * 6
