@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ARLIB_AMD_LIB') or os.path.join(_HERE, 'lib', 'libarlib_amd.so')      # override: developer builds (e.g. `make prof`)
-ABI_VERSION = 32
+ABI_VERSION = 33
 _lib = None
 
 
@@ -134,6 +134,12 @@ _SIGS = {
     'arl_kmeans_update_f32': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'arl_kmeans_sum_workspace_bytes': (_i64, []),
     'arl_kmeans_sum_f64': (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    'arl_kmeanspp_spans': (_i64, [_i64]),
+    'arl_kmeanspp_span_rows': (_i64, [_i64]),
+    'arl_kmeanspp_workspace_bytes': (_i64, [_i64, _i64]),
+    'arl_kmeanspp_dist_f32': (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'arl_kmeanspp_pick_f64': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'arl_kmeanspp_f32': (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'arl_corating_max_items': (_i64, []),
     'arl_corating_degree_i32': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     'arl_comm_load': (C.c_int, [C.c_char_p]),

@@ -1,6 +1,7 @@
 """Lloyd's k-means on the device (csrc/arl_kmeans.hip; reference recommender/NCL.py:52-73, e_step / run_kmeans) as tensor-level ops: the assign
-and update passes, the start the reference's sklearn call would draw from, and the loop.  NCL's opt-in `kmeans = 'device'` back end; a module of
-its own like arlib_amd/colsoftmax.py, with its poisoned-memory sweep in tests/test_gpu_kmeans_poison.py.  DESIGN.md section 3g has the rules."""
+and update passes, the random-rows start (the k-means++ start lives in arlib_amd/seeding.py), and the loop.  NCL's opt-in `kmeans = 'device'` back
+end; a module of its own like arlib_amd/colsoftmax.py, with its poisoned-memory sweep in tests/test_gpu_kmeans_poison.py.  DESIGN.md section 3g
+has the rules."""
 import numpy as np
 import torch
 
@@ -81,7 +82,8 @@ def kmeans_init_indices(N, k):
 
 
 def kmeans(X, k, n_iter=20, init=None):
-    """Lloyd's k-means of the rows of X [N, d] (float32, on the GPU) into k clusters.  Start: `init` [k, d], else X[kmeans_init_indices(N, k)].
+    """Lloyd's k-means of the rows of X [N, d] (float32, on the GPU) into k clusters.  Start: `init` [k, d], or 'k-means++' for
+    X[seeding.kmeanspp(X, k)] (sklearn's greedy k-means++ on the device), else X[kmeans_init_indices(N, k)].
     Every pass assigns (kmeans_assign) and, unless the pass changed no label (one integer read back per pass) or n_iter updates are done, updates
     (kmeans_update); the last pass is an assign against the final centroids, so labels and centroids agree (as kmeans.predict(x), NCL.py:73).
     Returns (centroids float32 [k, d], labels int64 [N], inertia: list with one float per assign pass, number of updates run).  An empty cluster
@@ -91,12 +93,17 @@ def kmeans(X, k, n_iter=20, init=None):
         raise ValueError('kmeans: k = %d, at least one cluster needed' % k)
     if n_iter < 0:
         raise ValueError('kmeans: n_iter = %d' % n_iter)
+    if isinstance(init, str) and init != 'k-means++':
+        raise ValueError("kmeans: init must be None, 'k-means++' or a [k, d] tensor, got %r" % (init,))
     if isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[0] < k:
         raise ValueError('kmeans: n_samples=%d should be >= n_clusters=%d' % (X.shape[0], k))
     X = _table(X, 'X', 'kmeans')
     N, d = X.shape
     if init is None:
         C = X[torch.from_numpy(kmeans_init_indices(N, k).astype(np.int64)).to(X.device)]
+    elif isinstance(init, str):
+        from . import seeding
+        C = X[seeding.kmeanspp(X, k)]
     else:
         C = _table(init, 'init', 'kmeans')
         if C.shape != (k, d) or C.device != X.device:

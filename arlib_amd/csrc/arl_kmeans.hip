@@ -1,4 +1,5 @@
-// arl_kmeans.hip -- Lloyd's k-means for NCL's prototype step (reference recommender/NCL.py:52-73: e_step / run_kmeans) on gfx950.
+// arl_kmeans.hip -- Lloyd's k-means for NCL's prototype step (reference recommender/NCL.py:52-73: e_step / run_kmeans) on gfx950, and the greedy
+// k-means++ start sklearn gives it (further down).
 //
 // One iteration is  assign: label[n] = argmax_c (<x_n, c> - 1/2 |c|^2)  (the nearest centroid; |x_n|^2 does not depend on c), then
 // update: C[c] = mean of the rows labelled c.  The inertia of an assign pass is  sum_n |x_n|^2 - 2 sum_n best[n].
@@ -213,7 +214,228 @@ __global__ __launch_bounds__(kBlk) void km_sum_fold_kernel(const double *__restr
     if (threadIdx.x == 0) out[0] = red[0];
 }
 
+// ---------------------------------------------------------------------------------------------------------------- greedy k-means++ start
+// (sklearn's _kmeans_plusplus with unit weights).  State: closest[n] = squared distance of row n to its nearest chosen centre.
+// A step measures every row against T <= 16 candidate rows (dist), then folds the potentials, takes the winner and draws the next candidates (pick).
+//   * distances are direct sums of squared differences (no |x|^2 - 2<x,c> + |c|^2: nothing cancels, the error is relative);
+//   * a workgroup owns a fixed span of rows (a multiple of kPpRows; at most kPpMaxSpans spans), four lanes share a row, a lane keeps every 4th float4
+//     of two rows (one at d = 128) in registers, the candidates sit in LDS; the potentials are double per lane, folded by a fixed shuffle tree and over the four waves in order;
+//   * the winner's minima are not copied: the next pass reads them where they lie, through the winner's index on the device;
+//   * every id and selector read from device memory is clamped before it addresses anything, and every comparison that finds a row is written so that
+//     a NaN leaves an index inside [0, N): ids address X afterwards.
+constexpr int kPpLanes = 4;                                   // lanes per row
+constexpr int kPpRows = 2 * kBlk / kPpLanes;                  // spans are multiples of the widest workgroup sweep (two rows per lane group)
+constexpr int kPpMaxSpans = 1024, kPpMaxT = 16;
+constexpr int kPickBlk = 64 * kPpMaxT;                        // one wave per candidate
+constexpr int kPickRows = 8;                                  // rows per lane in flight in the walk inside a span
+
+inline int kpp_span(long long N) {
+    const long long per = (N + kPpMaxSpans - 1) / kPpMaxSpans;
+    return (int)((per + kPpRows - 1) / kPpRows * kPpRows);
+}
+
+__device__ inline int kpp_clamp(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }          // an int is never a NaN: always inside [0, n)
+
+// mins[t][n] = min(closest[n], |x_n - x_{id_t}|^2) (closest = +inf without closest_base), part[t][b] = the sum of mins[t] over span b in double.
+// TT >= T candidates are computed (the surplus repeats the last one and is not stored); closest = closest_base + sel[0] * N.
+template <int D, int TT>
+__global__ __launch_bounds__(kBlk, 4) void kpp_dist_kernel(const float *__restrict__ X, int N, int span, const int32_t *__restrict__ cand_ids, int id0, int T,
+                                                            const float *__restrict__ closest_base, const int32_t *__restrict__ sel, int n_sel,
+                                                            float *__restrict__ mins, double *__restrict__ part, int S) {
+    constexpr int Q = D / (4 * kPpLanes), D4 = D / 4, R = D == 128 ? 1 : 2, G = kBlk / kPpLanes;      // R rows per lane group and sweep
+    __shared__ float4 cand[TT * D4];
+    __shared__ double wred[kPpMaxT][kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, j = tid & (kPpLanes - 1), g = tid / kPpLanes;
+    const float4 *X4 = reinterpret_cast<const float4 *>(X);
+    for (int i = tid; i < TT * D4; i += kBlk) {
+        const int t = min(i / D4, T - 1);
+        const int id = kpp_clamp(cand_ids ? cand_ids[t] : id0, N);
+        cand[i] = X4[(size_t)id * D4 + (i % D4)];
+    }
+    const float *closest = nullptr;
+    if (closest_base) closest = closest_base + (size_t)kpp_clamp(sel ? sel[0] : 0, n_sel) * N;
+    __syncthreads();
+    double pot[TT];
+#pragma unroll
+    for (int t = 0; t < TT; ++t) pot[t] = 0.0;
+    const int begin = blockIdx.x * span, end = min(N, begin + span);
+    for (int r0 = begin + g; r0 < end + g; r0 += R * G) {              // every lane runs every sweep: the shuffles below need the whole wave
+        asm volatile("" ::: "memory");                               // the candidates are read from LDS in every sweep: hoisted out of the loop they cost T D / 4 registers
+        float4 x[R][Q];
+        float cl[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const int r = r0 + i * G;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) x[i][q] = r < end ? X4[(size_t)r * D4 + q * kPpLanes + j] : make_float4(0.f, 0.f, 0.f, 0.f);
+            cl[i] = closest && j == 0 && r < end ? closest[r] : INFINITY;
+        }
+#pragma unroll
+        for (int t = 0; t < TT; ++t) {
+            float s[R];
+#pragma unroll
+            for (int i = 0; i < R; ++i) s[i] = 0.f;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const float4 c = cand[t * D4 + q * kPpLanes + j];
+#pragma unroll
+                for (int i = 0; i < R; ++i) {
+                    float e;
+                    e = x[i][q].x - c.x; s[i] = fmaf(e, e, s[i]);
+                    e = x[i][q].y - c.y; s[i] = fmaf(e, e, s[i]);
+                    e = x[i][q].z - c.z; s[i] = fmaf(e, e, s[i]);
+                    e = x[i][q].w - c.w; s[i] = fmaf(e, e, s[i]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                s[i] += __shfl_xor(s[i], 1);
+                s[i] += __shfl_xor(s[i], 2);
+                const int r = r0 + i * G;
+                if (t < T && j == 0 && r < end) {
+                    const float m = cl[i] <= s[i] ? cl[i] : s[i];          // numpy's minimum: a NaN distance stays a NaN
+                    mins[(size_t)t * N + r] = m;
+                    pot[t] += (double)m;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < TT; ++t) {
+        if (t < T) {
+            double v = pot[t];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+            if (lane == 0) wred[t][wv] = v;
+        }
+    }
+    __syncthreads();
+    if (tid < T) part[(size_t)tid * S + blockIdx.x] = ((wred[tid][0] + wred[tid][1]) + wred[tid][2]) + wred[tid][3];
+}
+
+__device__ inline double kpp_wave_scan(double v, int lane) {                      // inclusive, over the 64 lanes
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double o = __shfl_up(v, off);
+        if (lane >= off) v += o;
+    }
+    return v;
+}
+
+// One workgroup, wave t for candidate t.  pot_t = the fold of part[t] (a lane's strided spans, then a shuffle tree); the winner is the lowest t with the
+// smallest pot_t (a NaN never compares smaller: the winner stays inside [0, T)); sel_out = that t, index_out = its row.  With T_next > 0 wave j draws
+// next_ids[j]: the first row whose inclusive running sum of the winner's minima reaches u[j] * pot_winner -- a double prefix over the winner's span
+// partials, a bisection for the span, a walk inside it; no span reaches it: row N - 1; the walk does not (rounding between the two orders): the span's last row.
+__global__ __launch_bounds__(kPickBlk) void kpp_pick_kernel(const float *__restrict__ mins, const double *__restrict__ part, int N, int S, int span, int T,
+                                                             const int32_t *__restrict__ cand_ids, int id0, const double *__restrict__ u, int T_next,
+                                                             int32_t *__restrict__ next_ids, int32_t *__restrict__ sel_out, int32_t *__restrict__ index_out,
+                                                             int32_t *__restrict__ trace_ids, double *__restrict__ trace_pot, float *__restrict__ closest_out) {
+    __shared__ double s_pot[kPpMaxT], s_wtot[kPpMaxT], s_inc[kPpMaxSpans];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (wv < T) {
+        double v = 0.0;
+        for (int s = lane; s < S; s += 64) v += part[(size_t)wv * S + s];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == 0) s_pot[wv] = v;
+    }
+    __syncthreads();
+    int win = 0;
+    double best = s_pot[0];
+    for (int t = 1; t < T; ++t) {
+        const double p = s_pot[t];
+        if (p < best) { best = p; win = t; }
+    }
+    if (tid < T) {
+        const int id = kpp_clamp(cand_ids ? cand_ids[tid] : id0, N);
+        if (trace_ids) trace_ids[tid] = id;
+        if (trace_pot) trace_pot[tid] = s_pot[tid];
+        if (tid == win) { sel_out[0] = win; index_out[0] = id; }
+    }
+    const float *m = mins + (size_t)win * N;
+    if (closest_out)
+        for (int n = tid; n < N; n += kPickBlk) closest_out[n] = m[n];
+    if (T_next <= 0) return;
+    const double inc = kpp_wave_scan(tid < S ? part[(size_t)win * S + tid] : 0.0, lane);
+    if (lane == 63) s_wtot[wv] = inc;
+    __syncthreads();
+    double before = 0.0;
+    for (int w = 0; w < wv; ++w) before += s_wtot[w];
+    s_inc[tid] = before + inc;
+    __syncthreads();
+    if (wv >= T_next) return;
+    const double r = u[wv] * best;
+    int lo = 0, hi = S;                                    // the first span whose inclusive prefix is >= r; S if none is (or r is a NaN)
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s_inc[mid] >= r) hi = mid; else lo = mid + 1;
+    }
+    int id = N - 1;
+    if (lo < S) {
+        double base = lo > 0 ? s_inc[lo - 1] : 0.0;
+        const int begin = lo * span, end = min(N, begin + span);
+        id = end - 1;
+        bool found = false;
+        for (int c0 = begin; c0 < end && !found; c0 += 64 * kPickRows) {
+            float v[kPickRows];
+#pragma unroll
+            for (int q = 0; q < kPickRows; ++q) {
+                const int row = c0 + q * 64 + lane;
+                v[q] = row < end ? m[row] : 0.f;
+            }
+#pragma unroll
+            for (int q = 0; q < kPickRows; ++q) {
+                if (!found) {                              // the same in every lane
+                    const double run = base + kpp_wave_scan((double)v[q], lane);
+                    const unsigned long long hit = __ballot(c0 + q * 64 + lane < end && run >= r);
+                    if (hit) { id = c0 + q * 64 + __ffsll((long long)hit) - 1; found = true; }
+                    else base = __shfl(run, 63);
+                }
+            }
+        }
+    }
+    if (lane == 0) next_ids[wv] = kpp_clamp(id, N);
+}
+
 bool km_width(int64_t d) { return d == 16 || d == 32 || d == 64 || d == 128; }
+
+bool km_rows(int64_t n) { return n <= 0x7fffffffll / 128; }
+
+template <int D>
+int kpp_dist_run(const float *X, int64_t N, const int32_t *cand_ids, int id0, int T, const float *closest_base, const int32_t *sel, int n_sel, float *mins,
+                 double *part, hipStream_t st) {
+    const int span = kpp_span(N), S = (int)((N + span - 1) / span);
+#define KPP_DIST(TT)                                                                                                                         \
+    hipLaunchKernelGGL((kpp_dist_kernel<D, TT>), dim3((unsigned)S), dim3(kBlk), 0, st, X, (int)N, span, cand_ids, id0, T, closest_base, sel, n_sel, mins, part, S)
+    if (T <= 4) KPP_DIST(4);
+    else if (T <= 8) KPP_DIST(8);
+    else if (T <= 12) KPP_DIST(12);
+    else KPP_DIST(16);
+#undef KPP_DIST
+    KM_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
+int kpp_dist(const float *X, int64_t N, int64_t d, const int32_t *cand_ids, int id0, int T, const float *closest_base, const int32_t *sel, int n_sel, float *mins,
+             double *part, hipStream_t st) {
+    if (d == 16) return kpp_dist_run<16>(X, N, cand_ids, id0, T, closest_base, sel, n_sel, mins, part, st);
+    if (d == 32) return kpp_dist_run<32>(X, N, cand_ids, id0, T, closest_base, sel, n_sel, mins, part, st);
+    if (d == 64) return kpp_dist_run<64>(X, N, cand_ids, id0, T, closest_base, sel, n_sel, mins, part, st);
+    return kpp_dist_run<128>(X, N, cand_ids, id0, T, closest_base, sel, n_sel, mins, part, st);
+}
+
+int kpp_pick(const float *mins, const double *part, int64_t N, int T, const int32_t *cand_ids, int id0, const double *u, int T_next, int32_t *next_ids,
+             int32_t *sel_out, int32_t *index_out, int32_t *trace_ids, double *trace_pot, float *closest_out, hipStream_t st) {
+    const int span = kpp_span(N), S = (int)((N + span - 1) / span);
+    hipLaunchKernelGGL(kpp_pick_kernel, dim3(1), dim3(kPickBlk), 0, st, mins, part, (int)N, S, span, T, cand_ids, id0, u, T_next, next_ids, sel_out, index_out,
+                       trace_ids, trace_pot, closest_out);
+    KM_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
+// the whole-seeding workspace: part [T][S] double | ids [2][16] int32 | sel [4] int32 | mins [2][T][N] float
+constexpr int64_t kPpIdsBytes = 2 * kPpMaxT * sizeof(int32_t), kPpSelBytes = 16;
+int64_t kpp_part_bytes(int64_t N, int64_t T) { return ((int64_t)sizeof(double) * T * ((N + kpp_span(N) - 1) / kpp_span(N)) + 15) / 16 * 16; }
 
 template <int D>
 int km_assign_run(const float *X, int64_t N, const float *C, int64_t k, float *bias, int32_t *labels, float *score, hipStream_t st) {
@@ -280,6 +502,68 @@ int arl_kmeans_sum_f64(const float *v, int64_t n, int32_t squared, double *out, 
     hipLaunchKernelGGL(km_sum_fold_kernel, dim3(1), dim3(kBlk), 0, st, (const double *)workspace, (int)parts, out);
     KM_LAUNCH_CHECK();
     return ARL_OK;
+}
+
+int64_t arl_kmeanspp_spans(int64_t N) {
+    if (N <= 0 || !km_rows(N)) return 0;
+    return (N + kpp_span(N) - 1) / kpp_span(N);
+}
+
+int64_t arl_kmeanspp_span_rows(int64_t N) { return N <= 0 || !km_rows(N) ? 0 : kpp_span(N); }
+
+int64_t arl_kmeanspp_workspace_bytes(int64_t N, int64_t n_trials) {
+    if (N <= 0 || !km_rows(N) || n_trials < 1 || n_trials > kPpMaxT) return 0;
+    return kpp_part_bytes(N, n_trials) + kPpIdsBytes + kPpSelBytes + (int64_t)sizeof(float) * 2 * n_trials * N;
+}
+
+int arl_kmeanspp_dist_f32(const float *X, int64_t N, int64_t d, const int32_t *cand_ids, int64_t n_cand, const float *closest, float *mins, double *part,
+                          arl_stream_t stream) {
+    if (!X || !cand_ids || !mins || !part) return ARL_E_NULL;
+    if (!km_width(d)) return ARL_E_DIM;
+    if (N <= 0 || n_cand < 1 || n_cand > kPpMaxT) return ARL_E_ARG;
+    if (!km_rows(N)) return ARL_E_RANGE;
+    if (((uintptr_t)X & 15) || ((uintptr_t)part & 7)) return ARL_E_ARG;
+    return kpp_dist(X, N, d, cand_ids, 0, (int)n_cand, closest, nullptr, 1, mins, part, (hipStream_t)stream);
+}
+
+int arl_kmeanspp_pick_f64(const float *mins, const double *part, int64_t N, int64_t n_cand, const int32_t *cand_ids, const double *u, int64_t n_next,
+                          int32_t *next_ids, int32_t *winner, double *cand_pot, float *closest_out, arl_stream_t stream) {
+    if (!mins || !part || !cand_ids || !winner || !cand_pot || (n_next > 0 && (!u || !next_ids))) return ARL_E_NULL;
+    if (N <= 0 || n_cand < 1 || n_cand > kPpMaxT || n_next < 0 || n_next > kPpMaxT) return ARL_E_ARG;
+    if (!km_rows(N)) return ARL_E_RANGE;
+    if (((uintptr_t)part | (uintptr_t)u | (uintptr_t)cand_pot) & 7) return ARL_E_ARG;
+    return kpp_pick(mins, part, N, (int)n_cand, cand_ids, 0, u, (int)n_next, next_ids, winner, winner + 1, nullptr, cand_pot, closest_out, (hipStream_t)stream);
+}
+
+int arl_kmeanspp_f32(const float *X, int64_t N, int64_t d, int64_t k, int64_t n_trials, int64_t first, const double *u, int32_t *indices, float *closest,
+                     int32_t *cand_ids, double *cand_pot, void *workspace, arl_stream_t stream) {
+    if (!X || !indices || !closest || !workspace || (k > 1 && !u)) return ARL_E_NULL;
+    if (!km_width(d)) return ARL_E_DIM;
+    if (N <= 0 || k <= 0 || k > N || n_trials < 1 || n_trials > kPpMaxT || first < 0 || first >= N) return ARL_E_ARG;
+    if (!km_rows(N) || !km_rows(k)) return ARL_E_RANGE;
+    if ((((uintptr_t)X | (uintptr_t)workspace) & 15) || (((uintptr_t)u | (uintptr_t)cand_pot) & 7)) return ARL_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int T = (int)n_trials;
+    char *ws = (char *)workspace;
+    double *part = (double *)ws;
+    int32_t *ids = (int32_t *)(ws + kpp_part_bytes(N, T));
+    int32_t *sel = ids + 2 * kPpMaxT;
+    float *mins = (float *)(sel + 4);
+    const size_t half = (size_t)T * N;
+    // the first centre: closest = its distances (one candidate, no closest before it); the pick folds the potential and draws step 1's candidates
+    int rc = kpp_dist(X, N, d, nullptr, (int)first, 1, nullptr, nullptr, 1, mins, part, st);
+    if (rc != ARL_OK) return rc;
+    rc = kpp_pick(mins, part, N, 1, nullptr, (int)first, u, k > 1 ? T : 0, ids, sel, indices, nullptr, nullptr, k > 1 ? nullptr : closest, st);
+    for (int64_t c = 1; c < k && rc == ARL_OK; ++c) {
+        const int32_t *cur = ids + ((c - 1) & 1) * kPpMaxT;
+        float *out = mins + (c & 1) * half;
+        const bool last = c == k - 1;
+        rc = kpp_dist(X, N, d, cur, 0, T, mins + ((c - 1) & 1) * half, sel, T, out, part, st);
+        if (rc != ARL_OK) return rc;
+        rc = kpp_pick(out, part, N, T, cur, 0, last ? nullptr : u + c * T, last ? 0 : T, ids + (c & 1) * kPpMaxT, sel, indices + c,
+                      cand_ids ? cand_ids + (c - 1) * T : nullptr, cand_pot ? cand_pot + (c - 1) * T : nullptr, last ? closest : nullptr, st);
+    }
+    return rc;
 }
 
 }  // extern "C"

@@ -8,7 +8,8 @@ As executed by the reference:
 * the L2 term is divided by the batch size (NCL.py:147,157) -- `l2_scale`;
 * the context pass runs on `data.norm_adj` (the graph the DataLoader built), not on the encoder's current `sparse_norm_adj`;
 * `e_step` is sklearn's KMeans on the host from the global numpy RNG (same call here: same clusters), on the raw tables;
-  `kmeans = 'device'` (opt-in, or args.ncl_kmeans) runs Lloyd's iteration on the device instead (arlib_amd/cluster.py, DESIGN.md 3g);
+  `kmeans = 'device'` (opt-in, or args.ncl_kmeans) runs Lloyd's iteration on the device instead (arlib_amd/cluster.py), from
+  random rows or, with `kmeans_init = 'k-means++'` (args.ncl_kmeans_init), from the device k-means++ start (arlib_amd/seeding.py);
 * both phases step the optimiser (the commented `optimizer.step()` lines sit above the live one).
 
 The structure loss has B x U and B x I logits (2048 x 10^6 at cfg2): `_AllRowsNCE` walks the table in panels, twice (log-sum-exp,
@@ -132,6 +133,7 @@ class NCL(Recommender):
     fused_extra_loss = False
     l2_on_negatives = True
     kmeans = 'sklearn'                # e_step's back end: 'sklearn' (the reference's host call) or 'device' (arlib_amd.cluster.kmeans); args.ncl_kmeans overrides
+    kmeans_init = 'random'            # the device back end's start: 'random' (rows drawn as kmeans_init_indices) or 'k-means++' (arlib_amd.seeding); args.ncl_kmeans_init overrides
     adjgrad_through_views = True      # train(requires_adjgrad=True): only the main forward runs on sparse_norm_adj (NCL.py:134); the structure term's hops use a fresh tensor (:135)
 
     def __init__(self, args, data):
@@ -148,6 +150,9 @@ class NCL(Recommender):
         self.kmeans = getattr(args, 'ncl_kmeans', type(self).kmeans)
         if self.kmeans not in ('sklearn', 'device'):
             raise ValueError("NCL: kmeans must be 'sklearn' or 'device', got %r" % (self.kmeans,))
+        self.kmeans_init = getattr(args, 'ncl_kmeans_init', type(self).kmeans_init)
+        if self.kmeans_init not in ('random', 'k-means++'):
+            raise ValueError("NCL: kmeans_init must be 'random' or 'k-means++', got %r" % (self.kmeans_init,))
         self.reg = self.args.reg
         self.batch_size = self.args.batch_size
         self.model = LGCN_Encoder(self.data, self.args.emb_size, self.args.n_layers)
@@ -164,8 +169,9 @@ class NCL(Recommender):
         if self.kmeans == 'device':
             # Lloyd on the device tables themselves (no host copy); same dtypes and devices as the sklearn route below
             from .. import cluster
-            self.user_centroids, self.user_2cluster = cluster.kmeans(self.model.embedding_dict['user_emb'].detach(), self.k)[:2]
-            self.item_centroids, self.item_2cluster = cluster.kmeans(self.model.embedding_dict['item_emb'].detach(), self.k)[:2]
+            init = None if self.kmeans_init == 'random' else self.kmeans_init
+            self.user_centroids, self.user_2cluster = cluster.kmeans(self.model.embedding_dict['user_emb'].detach(), self.k, init=init)[:2]
+            self.item_centroids, self.item_2cluster = cluster.kmeans(self.model.embedding_dict['item_emb'].detach(), self.k, init=init)[:2]
             return
         self.user_centroids, self.user_2cluster = self.run_kmeans(self.model.embedding_dict['user_emb'].detach().cpu().numpy())
         self.item_centroids, self.item_2cluster = self.run_kmeans(self.model.embedding_dict['item_emb'].detach().cpu().numpy())

@@ -634,6 +634,32 @@ int64_t arl_kmeans_sum_workspace_bytes(void);
 int arl_kmeans_sum_f64(const float *v, int64_t n, int32_t squared, double *out, void *workspace, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Greedy k-means++ start for the k-means above (csrc/arl_kmeans.hip): sklearn's _kmeans_plusplus with unit weights, no host read inside the loop.
+ * State: closest [N] = squared distance of every row to its nearest chosen centre, pot = sum closest.  Step c = 1 .. k - 1: candidate t < n_trials
+ * is the first row whose inclusive running sum of closest reaches u[c - 1][t] * pot (row N - 1 if none does), mins[t][n] = min(closest[n],
+ * |x_n - x_cand_t|^2) as a direct sum of squared differences, pot_t = sum mins[t] in double over fixed spans; the lowest t with the smallest pot_t wins.
+ * Limits as above; n_trials in 1 .. 16 (else ARL_E_ARG), k <= N (else ARL_E_ARG).  Ids read from device memory are clamped into [0, N).
+ *   spans  : the number of row spans S of a table of N rows (the second extent of `part`) and the rows of a span (span b = rows [b rows, (b + 1) rows));
+ *            0 for N outside the limits.
+ *   dist   : one distance pass.  cand_ids [n_cand] (device), closest [N] or NULL (= +inf: the pass that forms closest from the first centre),
+ *            mins [n_cand][N], part [n_cand][S] double.
+ *   pick   : winner[0] = the winning t, winner[1] = its row, cand_pot [n_cand] = the folded potentials, closest_out [N] (may be NULL) = the winner's
+ *            minima, next_ids [n_next] = the candidates drawn with u [n_next] (n_next = 0: none; 0 .. 16).
+ *   whole  : arl_kmeanspp_f32 enqueues all k - 1 steps.  first = the first centre's row, u [(k - 1)][n_trials] double (device; unused for k = 1),
+ *            indices [k] int32, closest [N] = the final state, trace (both may be NULL): cand_ids [(k - 1)][n_trials], cand_pot likewise.
+ *            workspace: arl_kmeanspp_workspace_bytes(N, n_trials) bytes, 16-byte aligned like X; part, u and cand_pot 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t arl_kmeanspp_spans(int64_t N);
+int64_t arl_kmeanspp_span_rows(int64_t N);
+int64_t arl_kmeanspp_workspace_bytes(int64_t N, int64_t n_trials);
+int arl_kmeanspp_dist_f32(const float *X, int64_t N, int64_t d, const int32_t *cand_ids, int64_t n_cand, const float *closest, float *mins, double *part,
+                          arl_stream_t stream);
+int arl_kmeanspp_pick_f64(const float *mins, const double *part, int64_t N, int64_t n_cand, const int32_t *cand_ids, const double *u, int64_t n_next,
+                          int32_t *next_ids, int32_t *winner, double *cand_pot, float *closest_out, arl_stream_t stream);
+int arl_kmeanspp_f32(const float *X, int64_t N, int64_t d, int64_t k, int64_t n_trials, int64_t first, const double *u, int32_t *indices, float *closest,
+                     int32_t *cand_ids, double *cand_pot, void *workspace, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * GOAT's co-rating degree (csrc/arl_corating.hip).  Replaces attack/Gray/GOAT.py:37-39 (interact.T @ interact, every stored entry set to 1,
  * column sums): out[j] = the number of distinct items i (j included) that share a user with item j, 0 for an item nobody rated.  The product
  * is never formed: a workgroup owns one item and a bitmap of n_items bits in LDS, ORs the items of every user of j into it and popcounts.
