@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ARLIB_AMD_LIB') or os.path.join(_HERE, 'lib', 'libarlib_amd.so')      # override: developer builds (e.g. `make prof`)
-ABI_VERSION = 33
+ABI_VERSION = 34
 _lib = None
 
 
@@ -140,6 +140,10 @@ _SIGS = {
     'arl_kmeanspp_dist_f32': (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     'arl_kmeanspp_pick_f64': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     'arl_kmeanspp_f32': (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'arl_uniformity_splits': (_i64, [_i64]),
+    'arl_uniformity_workspace_bytes': (_i64, [_i64, _i64]),
+    'arl_uniformity_fwd_bwd_f32': (C.c_int, [_vp, _i64, _i64, _f, _f, _vp, _vp, _vp, _vp]),
+    'arl_alignment_fwd_bwd_f32': (C.c_int, [_vp, _vp, _i64, _i64, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     'arl_corating_max_items': (_i64, []),
     'arl_corating_degree_i32': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     'arl_comm_load': (C.c_int, [C.c_char_p]),

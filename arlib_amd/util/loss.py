@@ -1,10 +1,12 @@
-"""Loss functions with the reference's names and semantics (util/loss.py:5-15, 25-29, 42-49), computed by the HIP
+"""Loss functions with the reference's names and semantics (util/loss.py: all ten), computed by the HIP
 kernels and differentiable through torch.autograd (custom Functions; backward is another kernel, not autograd of
-ATen ops).  Inputs are GPU fp32 tensors; there is no CPU fallback (wrmf_loss alone also takes other tensors, as the reference function).
+ATen ops).  Inputs are GPU fp32 tensors; there is no CPU fallback (wrmf_loss, alignment_loss and uniformity_loss also take other tensors, as the
+reference functions; kl_divergence and js_divergence are on no model's path and are composed from torch ops).
 """
 import torch
+import torch.nn.functional as F
 
-from .. import ops
+from .. import ops, pairloss
 
 
 def _i32(t):
@@ -139,3 +141,78 @@ class _InfoNCE(torch.autograd.Function):
 def InfoNCE(view1, view2, temperature):
     """util/loss.py:42-49."""
     return _InfoNCE.apply(view1, view2, temperature)
+
+
+def batch_softmax_loss(user_emb, item_emb, temperature):
+    """util/loss.py:32-39: the arithmetic of InfoNCE (:42-49) under other argument names -- GPU fp32 rows run the same kernel within the same limits;
+    other tensors (CPU, float64) take the reference's own expression."""
+    if _kernel_rows(user_emb, item_emb):
+        return _InfoNCE.apply(user_emb, item_emb, temperature)
+    user_emb, item_emb = F.normalize(user_emb, dim=1), F.normalize(item_emb, dim=1)
+    pos = torch.exp((user_emb * item_emb).sum(dim=-1) / temperature)
+    ttl = torch.exp(torch.matmul(user_emb, item_emb.transpose(0, 1)) / temperature).sum(dim=1)
+    return torch.mean(-torch.log(pos / ttl))
+
+
+class _Alignment(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, alpha):
+        loss, dx, dy = pairloss.alignment(x.contiguous(), y.contiguous(), alpha, want_grad=True)
+        ctx.save_for_backward(dx, dy)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        dx, dy = ctx.saved_tensors
+        return (dx * gout if ctx.needs_input_grad[0] else None), (dy * gout if ctx.needs_input_grad[1] else None), None
+
+
+def alignment_loss(x, y, alpha=2):
+    """util/loss.py:17-19: mean_b ||normalize(x_b) - normalize(y_b)||^alpha.  GPU fp32 rows of a width the kernel covers run it (forward and both
+    gradients in one launch); other tensors (CPU, float64, other widths) take the reference's own expression."""
+    if _kernel_rows(x, y) and x.shape == y.shape and x.shape[1] % 4 == 0 and x.shape[1] <= pairloss.ALIGNMENT_MAX_WIDTH and x.shape[0] <= pairloss.PAIRLOSS_MAX_ROWS:
+        if not (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)):      # nobody will ask for the gradients: the forward launch alone
+            return pairloss.alignment(x.contiguous(), y.contiguous(), alpha, want_grad=False)[0][0].clone()
+        return _Alignment.apply(x, y, alpha)
+    x, y = F.normalize(x, dim=-1), F.normalize(y, dim=-1)
+    return (x - y).norm(p=2, dim=1).pow(alpha).mean()
+
+
+class _Uniformity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t):
+        loss, dx = pairloss.uniformity(x.contiguous(), t, want_grad=True)
+        ctx.save_for_backward(dx)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        (dx,) = ctx.saved_tensors
+        return dx * gout, None
+
+
+def uniformity_loss(x, t=2):
+    """util/loss.py:21-23: log mean_{i<j} exp(-t ||normalize(x_i) - normalize(x_j)||^2).  GPU fp32 rows of a width in pairloss.PAIRLOSS_WIDTHS, at
+    least two of them, run the streaming kernel (no pairwise-distance array); other tensors (CPU, float64, other widths, fewer than two rows -- where
+    the reference returns NaN) take the reference's own expression."""
+    if _kernel_rows(x) and x.shape[1] in pairloss.PAIRLOSS_WIDTHS and 2 <= x.shape[0] <= pairloss.PAIRLOSS_MAX_ROWS:
+        if not (torch.is_grad_enabled() and x.requires_grad):      # a diagnostic (no_grad, detached rows): half the work, no partial-tile workspace
+            return pairloss.uniformity(x.contiguous(), t, want_grad=False)[0][0].clone()
+        return _Uniformity.apply(x, t)
+    return torch.pdist(F.normalize(x, dim=-1), p=2).pow(2).mul(-t).exp().mean().log()
+
+
+def _kl_rows(a_logit, b_logit):
+    return torch.sum(F.softmax(a_logit, dim=-1) * (F.log_softmax(a_logit, dim=-1) - F.log_softmax(b_logit, dim=-1)), 1)
+
+
+def kl_divergence(p_logit, q_logit):
+    """util/loss.py:52-55: mean over rows of KL(softmax(p) || softmax(q)).  The reference's expression composed from torch ops: no model's path calls
+    it, so it has no kernel."""
+    return torch.mean(_kl_rows(p_logit, q_logit))
+
+
+def js_divergence(p_logit, q_logit):
+    """util/loss.py:57-62: mean over rows of KL(p || q) + KL(q || p) (the reference's symmetrised sum, not halved).  Composed from torch ops like
+    kl_divergence."""
+    return torch.mean(_kl_rows(p_logit, q_logit) + _kl_rows(q_logit, p_logit))

@@ -660,6 +660,31 @@ int arl_kmeanspp_f32(const float *X, int64_t N, int64_t d, int64_t k, int64_t n_
                      int32_t *cand_ids, double *cand_pot, void *workspace, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DirectAU's two terms (csrc/arl_pairloss.hip), forward and backward in one call each.  Replace util/loss.py:17-23 (alignment_loss,
+ * uniformity_loss) and their autograd.  Inputs are RAW rows; the calls normalise them (y = x / max(||x||, 1e-12), as F.normalize).
+ *   uniformity : loss[0] = log( mean_{i<j} exp(-t |y_i - y_j|^2) ) over the rows of X [n, d], dX [n, d] (NULL = forward only) = upstream * dloss/dX.
+ *                The reference stores n (n - 1) / 2 distances (torch.pdist); here no n x n array exists: dist^2 = max(q_i + q_j - 2 <y_i, y_j>, 0)
+ *                with q_r = |y_r|^2 kept per row (a zero row stays zero, rows are not assumed to have unit length), the scores exact fp32 on
+ *                v_mfma_f32_16x16x4_f32, the diagonal masked.  The gradient's two sums, rowsum_i = sum_j e_ij and G_i = sum_j e_ij y_j, cancel
+ *                in y_i rowsum_i - G_i, so they are summed in DOUBLE: G on v_mfma_f64_16x16x4_f64, at half the fp32 matrix rate (with dX the
+ *                call costs about 2.3 times the forward alone, not 2).  The streamed side is cut into arl_uniformity_splits(n) splits whose
+ *                partials are summed in split order, the total in double over fixed spans: bit-identical from run to run, no float atomics.
+ *                d in {16, 32, 64, 128} (else ARL_E_DIM), n >= 2 and t > 0 (else ARL_E_ARG), n <= 2^31 / 128 (else ARL_E_RANGE), X, dX and the
+ *                workspace 16-byte aligned (else ARL_E_ARG).  workspace: arl_uniformity_workspace_bytes(n, d) bytes (0 outside the limits); it
+ *                needs no initialisation.
+ *   alignment  : loss[0] = mean_b |x^_b - y^_b|^alpha over the row pairs of X, Y [n, d]; dX, dY [n, d] (both or neither) = upstream * dloss/d(X, Y).
+ *                A pair with x^_b == y^_b contributes gradient 0 (torch's subgradient of the norm at the origin).  One wave per pair, the mean
+ *                summed in double in a fixed order.  d % 4 == 0, d <= 256 (else ARL_E_DIM), n >= 1 and alpha > 0 (else ARL_E_ARG),
+ *                n <= 2^31 / 128 (else ARL_E_RANGE), 16-byte aligned tables.  terms [n]: scratch, receives the per-pair terms.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t arl_uniformity_splits(int64_t n);
+int64_t arl_uniformity_workspace_bytes(int64_t n, int64_t d);
+int arl_uniformity_fwd_bwd_f32(const float *X, int64_t n, int64_t d, float t, float upstream, float *loss, float *dX, void *workspace,
+                               arl_stream_t stream);
+int arl_alignment_fwd_bwd_f32(const float *X, const float *Y, int64_t n, int64_t d, float alpha, float upstream, float *loss, float *dX, float *dY,
+                              float *terms, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * GOAT's co-rating degree (csrc/arl_corating.hip).  Replaces attack/Gray/GOAT.py:37-39 (interact.T @ interact, every stored entry set to 1,
  * column sums): out[j] = the number of distinct items i (j included) that share a user with item j, 0 for an item nobody rated.  The product
  * is never formed: a workgroup owns one item and a bitmap of n_items bits in LDS, ORs the items of every user of j into it and popcounts.
