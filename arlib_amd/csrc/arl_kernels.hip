@@ -2640,31 +2640,89 @@ typedef __attribute__((address_space(3))) unsigned lds_u32;
 // product of two pieces is exact in fp32, and the dropped al*bl term is <= 2^-22 |a||b| -- 2^-21 per product in all, the size of the rounding
 // differences between two fp32 summation orders of a d = 64 dot product.  Scores, thresholds and the sorted lists live in the scaled domain
 // (scale = 2^(eu + ei), exact); only the final values are scaled back.
+//
+// THE CONTRACT of score_mask_topk (both paths; tests/test_topk_split_cpu.py restates the split in numpy, tests/test_gpu_topk_range.py holds the
+// kernels to it).  For every returned pair (u, i):   |val - float64 score| <= gamma_d |a_u| |b_i|,   gamma_d = d 2^-24 + 2^-21
+// (the any-order fp32 dot-product bound plus the dropped al*bl term: 4.3e-6 at d = 64, 8.1e-6 at d = 128), and an item i of the float64 list that
+// is missing from ours was displaced by a near-tie j:   ref[u,i] - ref[u,j] <= gamma_d |a_u| (|b_i| + |b_j|).
+// The split honours this only while the low pieces keep their bits.  ONE scale per table: an element 2^-G of the table's maximum has a low piece
+// on the subnormal fp16 grid (2^-24 in the scaled domain), whose rounding error 2^-25 is ABSOLUTE -- it scales with the table's largest element,
+// not with the row.  For a row whose largest element is 2^(13-G) in the scaled domain the three-product score of a pair is off by up to
+// sqrt(d) 2^-25 |b'| <= sqrt(d) 2^(G-38) |a'||b'|: within gamma_d / 2 for G <= kSplitSpreadLog2 = 16 at d = 64 and 128, past it at 17 (the
+// restatement's numbers are in the CPU test's docstring).  And the scale itself is clamped (split_scale), so a table whose largest magnitude has an
+// exponent outside [-27, 53] does not reach [2^13, 2^14) at all.  Hence the GATE, on the device (stage_sufmax_kernel, split_table_ok): a call whose
+// tables have a nonzero row with a largest element below 2^-16 of its table's, or a table exponent outside the clamp, leaves the split builds at
+// once and the exact-fp32 build of the kernel writes the same outputs (error d 2^-24 |a||b|, no table-wide scale).  All-zero rows do not count:
+// their pieces and scores are exact zeros.  Non-finite tables are outside the contract and stay where they were, on the split path.
+constexpr int kSplitSpreadLog2 = 16;
 
-// largest |x| of a table as float bits (non-negative floats order like unsigned ints): *out must be zeroed first
-__global__ __launch_bounds__(kBlock) void absmax_bits_kernel(const float *__restrict__ X, long long n, unsigned *__restrict__ out) {
-    // 16-byte loads, one atomic per WORKGROUP: 65 K same-address atomics (one per wave of the old form) serialise at ~12 ns each -- 0.8 ms
+// per table, in one pass over its rows (L = d / 4 lanes a row, d = 64 or 128): the largest |x| as float bits (non-negative floats order like unsigned
+// ints) -> atomic maximum at out[0], and the SMALLEST NONZERO row maximum -> atomic maximum of its complemented bits at out[2] (0 = no nonzero row).
+// Both words must be zeroed first.  One launch for both tables: workgroups [0, grid_a) take table A into out[0] / out[2], the others table B into
+// out[1] / out[3].
+// maximum over the 16 lanes of a DPP row, in every lane of it: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror -- vector-unit
+// moves (four ds_bpermute round trips per 16 loaded bytes made the maxima pass twice as long)
+__device__ __forceinline__ unsigned row16_max(unsigned v) {
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false));
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, false));
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0x141, 0xf, 0xf, false));
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0x140, 0xf, 0xf, false));
+    return v;
+}
+template <int L>
+__global__ __launch_bounds__(kBlock) void absmax_bits_kernel(const float *__restrict__ Xa, long long rows_a, const float *__restrict__ Xb, long long rows_b,
+                                                              unsigned grid_a, unsigned *__restrict__ out) {
+    // 16-byte loads, one atomic pair per WORKGROUP: 65 K same-address atomics (one per wave of the old form) serialise at ~12 ns each -- 0.8 ms
     // for a 256 MB table that streams in 50 us
-    __shared__ unsigned part[kWavesPerBlock];
-    unsigned m = 0u;
+    __shared__ unsigned part[2 * kWavesPerBlock];
+    const bool second = blockIdx.x >= grid_a;                      // (uniform per workgroup)
+    const float *__restrict__ X = second ? Xb : Xa;
+    const long long rows = second ? rows_b : rows_a;
+    const unsigned bid = second ? blockIdx.x - grid_a : blockIdx.x, nb = second ? gridDim.x - grid_a : grid_a;
+    unsigned m = 0u, nmin = 0u;
     const bool al = ((uintptr_t)X & 15u) == 0;
-    const long long n4 = al ? n / 4 : 0;
-    const float4 *X4 = reinterpret_cast<const float4 *>(X);
-    for (long long t = (long long)blockIdx.x * kBlock + threadIdx.x; t < n4; t += (long long)gridDim.x * kBlock) {
-        const float4 v = X4[t];
-        m = max(max(m, __float_as_uint(fabsf(v.x))), max(__float_as_uint(fabsf(v.y)), max(__float_as_uint(fabsf(v.z)), __float_as_uint(fabsf(v.w)))));
-    }
-    for (long long t = n4 * 4 + (long long)blockIdx.x * kBlock + threadIdx.x; t < n; t += (long long)gridDim.x * kBlock) m = max(m, __float_as_uint(fabsf(X[t])));
+    constexpr int rpb = kBlock / L;                                // rows per workgroup and turn (16 or 32 lanes a row: a row never straddles two waves)
+    const int sub = (int)threadIdx.x / L, j = (int)threadIdx.x % L;
+    constexpr int UN = 4;                                          // rows per lane group and turn: independent loads in flight, as the plain maximum had
+    auto pass = [&](auto aligned) {
+        for (long long base = (long long)bid * (rpb * UN); base < rows; base += (long long)nb * (rpb * UN)) {      // (uniform trip count: every lane runs the row maxima)
+            float4 v[UN];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+            for (int q = 0; q < UN; ++q) {                          // no branch around a load (each would wait for its own): rows past the end re-read the last row
+                const long long r = min(base + q * rpb + sub, rows - 1);
+                const float *x = X + r * (4 * L) + 4 * j;
+                if constexpr (decltype(aligned)::value) v[q] = *reinterpret_cast<const float4 *>(x);
+                else v[q] = make_float4(x[0], x[1], x[2], x[3]);
+            }
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                unsigned rm = max(max(__float_as_uint(fabsf(v[q].x)), __float_as_uint(fabsf(v[q].y))), max(__float_as_uint(fabsf(v[q].z)), __float_as_uint(fabsf(v[q].w))));
+                rm = row16_max(rm);
+                if (L == 32) rm = max(rm, (unsigned)__shfl_xor((int)rm, 16));
+                m = max(m, rm);
+                if (rm) nmin = max(nmin, ~rm);
+            }
+        }
+    };
+    if (al) pass(std::true_type{}); else pass(std::false_type{});
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { m = max(m, (unsigned)__shfl_xor((int)m, off)); nmin = max(nmin, (unsigned)__shfl_xor((int)nmin, off)); }
+    if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6] = m; part[kWavesPerBlock + (threadIdx.x >> 6)] = nmin; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < kWavesPerBlock; ++w) m = max(m, part[w]);
-        if (m) atomicMax(out, m);
+        for (int w = 1; w < kWavesPerBlock; ++w) { m = max(m, part[w]); nmin = max(nmin, part[kWavesPerBlock + w]); }
+        if (m) { atomicMax(out + (second ? 1 : 0), m); atomicMax(out + (second ? 3 : 2), nmin); }
     }
 }
-// power of two that brings a table whose largest magnitude has float bits `mbits` into [2^13, 2^14) (1 for an all-zero or non-finite table)
+// 1 when the split honours the contract above on a table with these two words (largest magnitude, complement of the smallest nonzero row maximum)
+__device__ __forceinline__ int split_table_ok(unsigned mbits, unsigned nminbits) {
+    const int e = (int)(mbits >> 23);
+    if (mbits == 0u || e >= 255) return 1;                         // all-zero: exact zeros; non-finite: outside the contract
+    if (e < 127 - 27 || e > 127 + 53) return 0;                    // the clamp of split_scale (subnormal maxima included)
+    return __uint_as_float(~nminbits) * (float)(1 << kSplitSpreadLog2) >= __uint_as_float(mbits);       // (a flushed subnormal row maximum compares as 0: exact path)
+}
+// power of two that brings a table whose largest magnitude has float bits `mbits` into [2^13, 2^14) (1 for an all-zero or non-finite table);
+// only a table whose exponent lies in [-27, 53] gets there (the gate above sends the others to the exact build)
 __device__ __forceinline__ float split_scale(unsigned mbits) {
     const int e = (int)(mbits >> 23);                              // biased exponent of the maximum
     if (e == 0 || e >= 255) return 1.f;
@@ -2720,7 +2778,11 @@ constexpr int kExitEvery = 8;                    // the exact early exit of the 
 // exit is enabled when the stage at 7/8 of the stream lies below half of the stage that holds the 4096th largest norm (where the bootstrap sample ends:
 // the region the first thresholds come from): measured on 1 M x 100 K, i.i.d. normal tables (ratio 0.73) and one-hop propagated tables (0.58) skip nothing
 // and keep the plain build; log-normal item norms (0.05) skip 84 % of the stream.
-__global__ __launch_bounds__(kWave) void stage_sufmax_kernel(const float *__restrict__ sn, int nst, float *__restrict__ out, int mst, int *__restrict__ pick) {
+// pick[2] / pick[3]: 1 / 0 when both tables are within the split's contract (split_table_ok; mbits = [items' maximum, users', items' smallest nonzero
+// row maximum complemented, users']), 0 / 1 otherwise: pick[2] gates a lone plain build, pick[3] the exact-fp32 build that then writes the outputs;
+// pick[0] and pick[1] are 0 with pick[3] set.
+__global__ __launch_bounds__(kWave) void stage_sufmax_kernel(const float *__restrict__ sn, int nst, float *__restrict__ out, int mst, int *__restrict__ pick,
+                                                              const unsigned *__restrict__ mbits) {
     const int lane = threadIdx.x;
     if (pick != nullptr) {                                          // (suffix maxima of the two stages, so that a stream in any other order than by norm keeps the plain build)
         const int head = min(nst - 1, 4096 / mst), tail = min(nst - 1, nst - nst / 8);
@@ -2730,7 +2792,8 @@ __global__ __launch_bounds__(kWave) void stage_sufmax_kernel(const float *__rest
         for (int off = 32; off > 0; off >>= 1) { mh = fmaxf(mh, __shfl_xor(mh, off)); mt = fmaxf(mt, __shfl_xor(mt, off)); }
         if (lane == 0) {
             const int on = head < tail && mt < 0.5f * mh;
-            pick[0] = on; pick[1] = !on;
+            const int ok = split_table_ok(mbits[0], mbits[2]) && split_table_ok(mbits[1], mbits[3]);
+            pick[0] = ok && on; pick[1] = ok && !on; pick[2] = ok; pick[3] = !ok;
         }
     }
     float carry = 0.f;
@@ -5184,11 +5247,11 @@ int arl_score_mask_topk_f32(const float *Pu, const float *Pi, int64_t U, int64_t
         const bool split = workspace != nullptr && (d == 64 || d == 128);
         const int mst = d <= 16 ? 128 : (d <= 64 ? 64 : 32);
         const size_t stageb = 2 * (size_t)mst * (4 * (size_t)d / 2 + 16);     // two half images of mst rows (STAGEB in the kernel)
-        const int nwaves = topk_waves((int)d, split);
-        const int users_per_wg = 16 * nwaves;
-        const size_t shm_m = kTopkRing * stageb + (2 * kTopkRing + kExitWords) * sizeof(unsigned) + sizeof(unsigned) * kQWords * nwaves +
-                             (mask_rowptr ? sizeof(unsigned) * users_per_wg * kBloomWords : 0);
-        const unsigned grid_m = (unsigned)((U + users_per_wg - 1) / users_per_wg);
+        int nwaves = topk_waves((int)d, split);
+        int users_per_wg = 16 * nwaves;
+        size_t shm_m = kTopkRing * stageb + (2 * kTopkRing + kExitWords) * sizeof(unsigned) + sizeof(unsigned) * kQWords * nwaves +
+                       (mask_rowptr ? sizeof(unsigned) * users_per_wg * kBloomWords : 0);
+        unsigned grid_m = (unsigned)((U + users_per_wg - 1) / users_per_wg);
         const void *image = Pi;
         const unsigned *max_bits = nullptr;
         const int32_t *order_d = nullptr;
@@ -5196,15 +5259,21 @@ int arl_score_mask_topk_f32(const float *Pu, const float *Pi, int64_t U, int64_t
         float *snorm_d = nullptr;
         unsigned long long *stats_d = nullptr;
         int *pick_d = nullptr;
+        const int *xgate = nullptr;                            // gate of the exact-fp32 build: none, or the split's fallback word (below)
         if (split) {
             const long long n = (long long)I * d;
-            // workspace: [I][2][d] fp16 image (4 I d bytes), then the two tables' largest magnitudes (float bits: items, users)
+            // workspace: [I][2][d] fp16 image (4 I d bytes), then four words: the two tables' largest magnitudes (float bits: items, users) and
+            // their smallest nonzero row maxima (complemented bits: items, users)
             unsigned *mb = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + 4 * (size_t)n);
-            if (hipMemsetAsync(mb, 0, 2 * sizeof(unsigned), (hipStream_t)stream) != hipSuccess) return ARL_E_ARG;
-            hipLaunchKernelGGL(absmax_bits_kernel, dim3(grid_for(n / 4 + 1, kBlock, 2048u)), dim3(kBlock), 0, (hipStream_t)stream, Pi, n, mb);
-            ARL_LAUNCH_CHECK();
-            hipLaunchKernelGGL(absmax_bits_kernel, dim3(grid_for(U * d / 4 + 1, kBlock, 2048u)), dim3(kBlock), 0, (hipStream_t)stream, Pu, (long long)(U * d), mb + 1);
-            ARL_LAUNCH_CHECK();
+            // ONE memset for every word of the workspace that must start at zero -- these four, the table maximum behind the stage norms, the pass's two
+            // counters -- from here to the end of the gate words: what lies between (inverse order, stage norms, suffix maxima, gates) is written afterwards
+            if (hipMemsetAsync(mb, 0, (size_t)arl_score_mask_topk_stats_offset(I, d) + 32 - 4 * (size_t)n, (hipStream_t)stream) != hipSuccess) return ARL_E_ARG;
+            {   // one launch for both tables
+                const unsigned ga = grid_for(n / 4 + 1, kBlock, 2048u), gb = grid_for(U * d / 4 + 1, kBlock, 2048u);
+                if (d == 64) hipLaunchKernelGGL(absmax_bits_kernel<16>, dim3(ga + gb), dim3(kBlock), 0, (hipStream_t)stream, Pi, (long long)I, Pu, (long long)U, ga, mb);
+                else hipLaunchKernelGGL(absmax_bits_kernel<32>, dim3(ga + gb), dim3(kBlock), 0, (hipStream_t)stream, Pi, (long long)I, Pu, (long long)U, ga, mb);
+                ARL_LAUNCH_CHECK();
+            }
             if (item_order) {                                  // the item stream in the caller's order: inverse map behind the two maxima (the 6 I d byte workspace has room)
                 order_d = item_order;
                 pos_d = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) + 4 * (size_t)n + 16);
@@ -5217,15 +5286,13 @@ int arl_score_mask_topk_f32(const float *Pu, const float *Pi, int64_t U, int64_t
             {   // per-stage and whole-table largest scaled row norms (the factor of the high-piece stream's bound), behind the inverse map's room
                 const int nst = (int)((I + mst - 1) / mst);
                 snorm_d = reinterpret_cast<float *>(static_cast<char *>(workspace) + 4 * (size_t)n + 16 + 4 * (size_t)I);
-                if (hipMemsetAsync(snorm_d + nst, 0, sizeof(float), (hipStream_t)stream) != hipSuccess) return ARL_E_ARG;
                 hipLaunchKernelGGL(stage_norm_kernel, dim3((unsigned)nst), dim3(kWave), 0, (hipStream_t)stream, Pi, (int)I, (int)d, mst, mb, order_d, nst, snorm_d);
                 ARL_LAUNCH_CHECK();
                 // behind them: the suffix maxima [nst + 1] (the early exit's bound) and two 8-byte counters (stream stages consumed, workgroups)
                 stats_d = reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + arl_score_mask_topk_stats_offset(I, d));
-                pick_d = reinterpret_cast<int *>(stats_d + 2);     // [exit build, plain build]
-                hipLaunchKernelGGL(stage_sufmax_kernel, dim3(1), dim3(kWave), 0, (hipStream_t)stream, snorm_d, nst, snorm_d + nst + 1, mst, pick_d);
+                pick_d = reinterpret_cast<int *>(stats_d + 2);     // [exit build, plain build, plain build alone, exact-fp32 build (the split's fallback)]
+                hipLaunchKernelGGL(stage_sufmax_kernel, dim3(1), dim3(kWave), 0, (hipStream_t)stream, snorm_d, nst, snorm_d + nst + 1, mst, pick_d, (const unsigned *)mb);
                 ARL_LAUNCH_CHECK();
-                if (hipMemsetAsync(stats_d, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) return ARL_E_ARG;      // (before the kernels; the two gate words behind them are written by stage_sufmax_kernel)
             }
             ARL_LAUNCH_CHECK();
             image = workspace;
@@ -5241,9 +5308,9 @@ int arl_score_mask_topk_f32(const float *Pu, const float *Pi, int64_t U, int64_t
 #define ARL_TOPK_CASE2_true(DV, WM, WARMP, GATE)                                                                                       \
         do {                                                                                                                           \
             if (exit_mode != 0) { ARL_TOPK_CASE3(DV, true, WM, true, WARMP, GATE, (const int *)pick_d); ARL_TOPK_CASE3(DV, true, WM, false, WARMP, GATE, (const int *)(pick_d + 1)); } \
-            else ARL_TOPK_CASE3(DV, true, WM, false, WARMP, GATE, (const int *)nullptr);                                                \
+            else ARL_TOPK_CASE3(DV, true, WM, false, WARMP, GATE, (const int *)(pick_d + 2));                                           \
         } while (0)
-#define ARL_TOPK_CASE2_false(DV, WM, WARMP, GATE) ARL_TOPK_CASE3(DV, false, WM, false, WARMP, GATE, (const int *)nullptr)
+#define ARL_TOPK_CASE2_false(DV, WM, WARMP, GATE) ARL_TOPK_CASE3(DV, false, WM, false, WARMP, GATE, xgate)
         /* a warm-started call is followed by its own cold repeat, gated on the underflow flag on the device: valid results without a host round trip */
 #define ARL_TOPK_CASE(DV, SP)                                                                                                          \
         do {                                                                                                                           \
@@ -5281,11 +5348,11 @@ int arl_score_mask_topk_f32(const float *Pu, const float *Pi, int64_t U, int64_t
             do {                                                                                                                       \
                 if (WARMF) {                                                                                                           \
                     hipLaunchKernelGGL(topk2_warm_kernel, dim3(grid_for(U, kWavesPerBlock, 8192u)), dim3(kBlock), 0, st, Pu, Pi, (int)U, (int)I, (int)d, (int)k, mask_rowptr, warm_idx, max_bits, thr0, GATE, \
-                                       (const int *)nullptr);                                                                          \
+                                       (const int *)(pick_d + 2));                                                                        \
                     ARL_LAUNCH_CHECK();                                                                                                \
                 }                                                                                                                      \
                 if (exit_mode != 0) { ARL_TOPK2_MAIN(DV, true, WARMF, GATE, (const int *)pick_d); ARL_TOPK2_MAIN(DV, false, WARMF, GATE, (const int *)(pick_d + 1)); } \
-                else ARL_TOPK2_MAIN(DV, false, WARMF, GATE, (const int *)nullptr);                                                     \
+                else ARL_TOPK2_MAIN(DV, false, WARMF, GATE, (const int *)(pick_d + 2));                                                \
             } while (0)
 #define ARL_TOPK2_CALL(DV)                                                                                                             \
             do {                                                                                                                       \
@@ -5301,6 +5368,18 @@ int arl_score_mask_topk_f32(const float *Pu, const float *Pi, int64_t U, int64_t
         else if (d == 32) ARL_TOPK_CASE(32, false);
         else if (d == 64) { if (split) ARL_TOPK_CASE(64, true); else ARL_TOPK_CASE(64, false); }
         else { if (split) ARL_TOPK_CASE(128, true); else ARL_TOPK_CASE(128, false); }
+        if (split) {
+            // the split's fallback: the exact-fp32 build (the exact = true call: table-order stream of the fp32 rows, its own warm start and cold repeat),
+            // gated on pick[3] -- tables outside the split's contract (kSplitSpreadLog2, the clamp of split_scale); it returns at once on every other call
+            ARL_LAUNCH_CHECK();
+            xgate = pick_d + 3;
+            image = Pi; max_bits = nullptr; order_d = nullptr; pos_d = nullptr; snorm_d = nullptr; stats_d = nullptr;
+            nwaves = topk_waves((int)d, false); users_per_wg = 16 * nwaves;
+            shm_m = kTopkRing * stageb + (2 * kTopkRing + kExitWords) * sizeof(unsigned) + sizeof(unsigned) * kQWords * nwaves +
+                    (mask_rowptr ? sizeof(unsigned) * users_per_wg * kBloomWords : 0);
+            grid_m = (unsigned)((U + users_per_wg - 1) / users_per_wg);
+            if (d == 64) ARL_TOPK_CASE(64, false); else ARL_TOPK_CASE(128, false);
+        }
 #undef ARL_TOPK_CASE2_true
 #undef ARL_TOPK_CASE2_false
 #undef ARL_TOPK_CASE3

@@ -1364,8 +1364,15 @@ def _exit_probe_record(st, ws, off, nst):
 
 def score_mask_topk(Pu, Pi, k, mask_rowptr=None, mask_col=None, exact=False, warm_idx=None, item_order='norm'):
     """top-k of Pu @ Pi.T per user with an optional interacted-item mask (CSR over users), streamed.
-    exact=True: scores are the exact fp32 contraction; default: split-fp16 matrix path (two fp16 pieces of the power-of-two-scaled operands, three products) for d in {64, 128} (scores within
-    ~1e-6 relative, faster), exact otherwise.
+    exact=True: scores are the exact fp32 contraction; default: split-fp16 matrix path (two fp16 pieces of the power-of-two-scaled operands, three products) for d in {64, 128}
+    (faster), exact otherwise.
+    The contract, on either path: every returned pair (u, i) has |val - float64 score| <= gamma_d * |a_u| * |b_i| with gamma_d = d * 2^-24 + 2^-21 (4.3e-6 at
+    d = 64, 8.1e-6 at d = 128; exact=True: d * 2^-24 alone), and an item i of the float64 list that is missing from ours was displaced by a near-tie j:
+    ref[u, i] - ref[u, j] <= gamma_d * |a_u| * (|b_i| + |b_j|) (masked and padded tail entries aside).  The split scales each TABLE by one power of two, so
+    it keeps that bound only for rows that are not tiny next to their table: when a nonzero row's largest |element| is below 2^-16 of its table's, or a
+    table's largest magnitude has an exponent outside [-27, 53], the call is routed -- on the device, no host wait -- to the exact fp32 build, which
+    writes the same outputs (all-zero rows do not count; TOPK_STATS['record_route'] / topk_fallbacks() show the route).  Non-finite tables are outside the
+    contract.
     warm_idx: optional int32 [U, k] of DISTINCT candidate items per user (e.g. the previous call's result while the tables
     moved little): pre-sets the thresholds, same result, fewer inserts; if a candidate turned out masked the call is repeated
     cold automatically.
@@ -1443,6 +1450,9 @@ def score_mask_topk(Pu, Pi, k, mask_rowptr=None, mask_col=None, exact=False, war
         off = _lib.lib().arl_score_mask_topk_stats_offset(I, d)
         mst = 128 if d <= 16 else (64 if d <= 64 else 32)
         TOPK_STATS.setdefault('exit', []).append((ws[off:off + 16].clone(), (I + mst - 1) // mst))
+    if ws is not None and TOPK_STATS.get('record_route'):     # diagnostics: the pass's route words [split, exact fallback] (an 8-byte device copy, no synchronisation)
+        off = _lib.lib().arl_score_mask_topk_stats_offset(I, d)
+        TOPK_STATS.setdefault('route', []).append(ws[off + 24:off + 32].clone())
     # (a warm-started call repeats itself cold on the device when its flag is raised: nothing to wait for here; benches that count the repeats keep the flags)
     if flag is not None and TOPK_STATS.get('record_events'):
         TOPK_STATS.setdefault('flags', []).append(flag)
@@ -1458,6 +1468,15 @@ def topk_exit_fractions(reset=True):
         out.append(1.0 - consumed / float(max(1, wgs * nst)) if wgs else 0.0)
     if reset:
         TOPK_STATS['exit'] = []
+    return out
+
+
+def topk_fallbacks(reset=True):
+    """Per recorded pass of the split path (TOPK_STATS['record_route'] = True): True where the device routed the call to the exact fp32 build because a
+    table was outside the split's contract (see score_mask_topk).  Synchronises (reads the route words)."""
+    out = [bool(t.view(torch.int32)[1].item()) for t in TOPK_STATS.get('route', [])]
+    if reset:
+        TOPK_STATS['route'] = []
     return out
 
 

@@ -444,9 +444,13 @@ int arl_pga_update_f32(float *S, const float *grad, const float *dinv_rows, cons
  * workspace == NULL: scores are the exact fp32 contraction (bitwise an fmaf chain over d).
  * workspace != NULL (arl_score_mask_topk_workspace_bytes(I, d) bytes) and d in {64, 128}: the contraction runs on
  * the 16-bit matrix path with every fp32 operand (scaled by a power of two chosen per table on the device) split in
- * two fp16 pieces, three partial products accumulated in fp32 -- scores within ~1e-6 relative of the exact ones
- * (the size of fp32 summation-order differences), 3x faster; the workspace receives the split image of Pi and the
- * two tables' largest magnitudes.  Other d ignore the workspace.  (How the three products are scheduled is internal: the
+ * two fp16 pieces, three partial products accumulated in fp32, 3x faster; the workspace receives the split image of Pi, the
+ * two tables' largest magnitudes and their smallest nonzero row maxima.  Other d ignore the workspace.
+ * Contract (either path): every returned pair has |top_val - float64 score| <= (d 2^-24 + 2^-21) |Pu row| |Pi row| (d 2^-24 alone with
+ * workspace == NULL), and an item of the float64 list that is missing was displaced by a near-tie within that bound.  The split keeps it only
+ * for rows that are not tiny next to their table (one scale per table): if a nonzero row's largest |element| is below 2^-16 of its table's, or
+ * a table's largest magnitude has an exponent outside [-27, 53], the split builds return at once and the exact fp32 build writes the same
+ * outputs -- decided on the device, no host wait.  All-zero rows do not count; non-finite tables are outside the contract.  (How the three products are scheduled is internal: the
  * stream contracts the high pieces only, filters against threshold - E with E a rigorous bound on the two other products,
  * and every candidate that reaches a list is scored with all three -- the scores returned are those of the three-product form.)
  * warm_idx (optional, matrix-core path only): [U, k] DISTINCT candidate items per user, e.g. the previous call's top_idx when
@@ -463,7 +467,8 @@ int arl_pga_update_f32(float *S, const float *grad, const float *dinv_rows, cons
  * |a_u| * (largest norm of any later item) lies below the user's current k-th best score by more than the pre-filter's slack (Cauchy-Schwarz:
  * no later item can enter a list) -- the stages skipped cannot change the result, which stays that of the full stream bit for bit.  What was
  * skipped is readable after the pass: two uint64 counters at byte arl_score_mask_topk_stats_offset(I, d) of the workspace,
- * [stream stages consumed summed over workgroups, workgroups], followed by two int32 [exit build picked, plain build picked].
+ * [stream stages consumed summed over workgroups, workgroups], followed by four int32 [exit build picked, plain build picked, split path taken,
+ * exact fp32 fallback taken].
  * The exit's code costs the stream loop ~5 % where nothing can be skipped (the loop has no register to spare), so it lives in a second BUILD of
  * the kernel.  exit_mode = 1: both builds are launched and the device runs one of them, chosen from the items' norm profile (the exit build iff the
  * norms at 7/8 of the stream are below half of the 4096th largest); exit_mode = 0: the plain build alone (a caller that has seen the counters report

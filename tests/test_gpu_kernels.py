@@ -699,7 +699,7 @@ def test_score_mask_topk_bootstrap_threshold(ops, d, k):
         assert (val[:, :-1] >= val[:, 1:]).all()
         same = idx == ridx
         assert same.mean() > 0.999
-        for r, c in np.argwhere(~same):                  # differences are near-ties of the split-bf16 contraction
+        for r, c in np.argwhere(~same):                  # differences are near-ties of the split-fp16 contraction
             assert abs(rval[r, c] - val[r, c]) <= 1e-5 * max(1.0, abs(rval[r, c]))
         ex_i, ex_v = ops.score_mask_topk(T(Pu), T(Pi), k, T(rp) if masked else None, T(mc) if masked else None, exact=True)
         assert rel_err(ex_v.cpu().numpy(), rval.astype(np.float32)) < 1e-5 and (ex_i.cpu().numpy() == ridx).mean() > 0.999
