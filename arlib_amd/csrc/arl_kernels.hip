@@ -724,33 +724,148 @@ struct BlockedDev {
     const uint32_t *xbits;        // MASKED only: one bit per operand row; X is zero on the rows whose bit is clear
 };
 
-// spmm_epilogue for CPL adjacent columns per lane (d = 64 * CPL); same arithmetic (a wave writes one 256-B / 512-B row at a time)
-template <int MODE, int CPL, int LD>
-__device__ __forceinline__ void spmm_epilogue1(const Epi &ep, int row, int lane, const float *a) {
-    const size_t o = (size_t)row * LD + lane * CPL;
-    const bool zr = ep.Z && (!ep.zflags || ep.zflags[row]);
+// The blocked kernel's epilogue: spmm_epilogue's arithmetic for CPL adjacent columns per lane (d = 64 * CPL), taken apart into what a row
+// loads (`in`), what it computes and what it stores (`out`), so that a wave can have the loads of a whole group of output rows in flight
+// before it writes any of them.  `row`, `zr` (the row reads Z) and `rs` (the row's rscale entry) are wave-uniform.
+template <int MODE> constexpr int kEpiLoads = MODE == EPI_ADAM ? 4 : 1;                                  // Z | S_in | Z, P, M, V
+template <int MODE> constexpr int kEpiStores = MODE == EPI_ADAM ? 3 : MODE == EPI_LAYERSUM ? 2 : 1;      // Y | Y, S | P, M, V
+
+template <int MODE>
+__device__ __forceinline__ float *spmm_epilogue_table(const Epi &ep, int s) {
+    if (MODE == EPI_AXPBY) return ep.Y;
+    if (MODE == EPI_LAYERSUM) return s == 0 ? ep.Y : ep.S;
+    return s == 0 ? ep.P : s == 1 ? ep.M : ep.V;
+}
+
+template <int MODE, int CPL>
+__device__ __forceinline__ void spmm_epilogue_math(const Epi &ep, bool zr, float rs, const float *a, const float (&in)[kEpiLoads<MODE>][CPL],
+                                                   float (&out)[kEpiStores<MODE>][CPL]) {
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
-        if (MODE == EPI_AXPBY) {
-            float y = (ep.rscale ? ep.alpha * ep.rscale[row] : ep.alpha) * a[c];
-            if (zr) y = fmaf(ep.beta, ep.Z[o + c], y);
-            __builtin_nontemporal_store(y, ep.Y + o + c);
-        } else if (MODE == EPI_LAYERSUM) {
-            const float sv = ep.S_in[o + c];
-            if (ep.Y) ep.Y[o + c] = a[c];
-            ep.S[o + c] = sv + a[c];
+        // what rounds once is written as an fmaf and nothing else may be contracted: where this code is inlined must not decide the bits
+        // (m's and denom's products round on their own, v and p are fused multiply-adds: what the row-at-a-time build of this epilogue emitted)
+#pragma clang fp contract(off)
+        if constexpr (MODE == EPI_AXPBY) {
+            float y = (ep.rscale ? ep.alpha * rs : ep.alpha) * a[c];
+            if (zr) y = fmaf(ep.beta, in[0][c], y);
+            out[0][c] = y;
+        } else if constexpr (MODE == EPI_LAYERSUM) {
+            out[0][c] = a[c];
+            out[1][c] = in[0][c] + a[c];
         } else {
             float g = ep.alpha * a[c];
-            if (zr) g = fmaf(ep.beta, ep.Z[o + c], g);
-            float p = ep.P[o + c], m = ep.M[o + c], v = ep.V[o + c];
+            if (zr) g = fmaf(ep.beta, in[0][c], g);
+            float p = in[1][c], m = in[2][c], v = in[3][c];
             m = m + (g - m) * ep.w1;
-            v = v * ep.b2 + ep.w2 * g * g;
+            v = fmaf(ep.w2 * g, g, v * ep.b2);
             const float denom = sqrtf(v) / ep.bc2_sqrt + ep.eps;
-            p = p - ep.step_size * (m / denom);
-            ep.P[o + c] = p; ep.M[o + c] = m; ep.V[o + c] = v;
+            p = fmaf(-ep.step_size, m / denom, p);
+            out[0][c] = p; out[1][c] = m; out[2][c] = v;
         }
     }
 }
+
+// one row at a time: load, compute, store (every slot of the build that is not grouped; elsewhere the slots from a wave's first padding slot on)
+template <int MODE, int CPL, int LD>
+__device__ __forceinline__ void spmm_epilogue1(const Epi &ep, int row, bool zr, float rs, int lane, const float *a) {
+    const size_t o = (size_t)row * LD;                           // wave-uniform row base + 32-bit lane offset: scalar-base addressing
+    const unsigned lo = lane * CPL;
+    float in[kEpiLoads<MODE>][CPL], out[kEpiStores<MODE>][CPL];
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+        in[0][c] = 0.f;
+        if constexpr (MODE == EPI_LAYERSUM) in[0][c] = (ep.S_in + o)[lo + c];
+        else if (zr) in[0][c] = (ep.Z + o)[lo + c];
+        if constexpr (MODE == EPI_ADAM) { in[1][c] = (ep.P + o)[lo + c]; in[2][c] = (ep.M + o)[lo + c]; in[3][c] = (ep.V + o)[lo + c]; }
+    }
+    spmm_epilogue_math<MODE, CPL>(ep, zr, rs, a, in, out);
+#pragma unroll
+    for (int s = 0; s < kEpiStores<MODE>; ++s) {
+        if (MODE == EPI_LAYERSUM && s == 0 && !ep.Y) continue;
+        float *dst = spmm_epilogue_table<MODE>(ep, s) + o;
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+            if (MODE == EPI_AXPBY) __builtin_nontemporal_store(out[s][c], dst + (lo + c));
+            else dst[lo + c] = out[s][c];
+        }
+    }
+}
+
+// K slots at a time, slots r0 .. r0 + K - 1 of the wave, none of them padding, and NO branch around a load or a store: the compiler counts
+// the memory operations in flight along straight code only, and waits for all of them wherever a branch may have added one.  So a slot
+// that reads no Z (flag clear) or nothing at all (piece of a split row) loads from `safe_row`, a row of this wave, and drops the value;
+// a piece stores its raw sum to `partial` through the same store instructions (three times over with the Adam epilogue).  What is
+// left are conditions that hold for the whole launch (Z or Y not given), which skip K loads or K stores together.
+template <int MODE, int K, int CPL, int LD>
+__device__ __forceinline__ void spmm_group_load(const Epi &ep, int my_row, unsigned zmask, int safe_row, int r0, int lane, float (&in)[K][kEpiLoads<MODE>][CPL]) {
+    const unsigned lo = lane * CPL;                              // wave-uniform row base (selected as a pointer) + 32-bit lane offset: scalar-base addressing
+    const size_t so = (size_t)safe_row * LD;
+    if constexpr (MODE != EPI_LAYERSUM) {
+#pragma unroll
+        for (int i = 0; i < K; ++i)
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) in[i][0][c] = 0.f;
+        if (ep.Z) {
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                const int row = __builtin_amdgcn_readlane(my_row, r0 + i);
+                const float *z = ((zmask >> (r0 + i)) & 1u) ? ep.Z + (size_t)row * LD : ep.Z + so;
+#pragma unroll
+                for (int c = 0; c < CPL; ++c) in[i][0][c] = z[lo + c];
+            }
+        }
+    }
+    if constexpr (MODE != EPI_AXPBY) {
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            const int row = __builtin_amdgcn_readlane(my_row, r0 + i);
+            const size_t o = (size_t)row * LD;
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) {
+                if constexpr (MODE == EPI_LAYERSUM) in[i][0][c] = (row >= 0 ? ep.S_in + o : ep.S_in + so)[lo + c];
+                else {
+                    in[i][1][c] = (row >= 0 ? ep.P + o : ep.P + so)[lo + c];
+                    in[i][2][c] = (row >= 0 ? ep.M + o : ep.M + so)[lo + c];
+                    in[i][3][c] = (row >= 0 ? ep.V + o : ep.V + so)[lo + c];
+                }
+            }
+        }
+    }
+}
+
+template <int MODE, int K, int CPL, int LD>
+__device__ __forceinline__ void spmm_group_store(const Epi &ep, float *partial, int my_row, int r0, int lane, const float (&a)[K][CPL],
+                                                 const float (&out)[K][kEpiStores<MODE>][CPL]) {
+    const unsigned lo = lane * CPL;
+#pragma unroll
+    for (int s = 0; s < kEpiStores<MODE>; ++s) {
+        if (MODE == EPI_LAYERSUM && s == 0 && !ep.Y) continue;
+        float *tab = spmm_epilogue_table<MODE>(ep, s);
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            const int row = __builtin_amdgcn_readlane(my_row, r0 + i);
+            const bool plain = row >= 0;                          // else row < -1: piece of a split (hub) row, raw sum, combined by spmm_long_rows_kernel
+            float *dst = plain ? tab + (size_t)row * LD : partial + (size_t)(plain ? 0 : -row - 2) * (64 * CPL);
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) {
+                const float y = plain ? out[i][s][c] : a[i][c];
+                if (MODE == EPI_AXPBY) __builtin_nontemporal_store(y, dst + (lo + c));
+                else dst[lo + c] = y;
+            }
+        }
+    }
+}
+
+// Which builds take the grouped epilogue: the masked one and those with 16 loads in flight (launches of ~3 000 waves in one round, long
+// record streams: a wave's serial tail is the launch's tail).  The unmasked build with 32 loads in flight keeps the row-at-a-time
+// epilogue: its launches (cfg2's 31 250 user-row waves, six rounds) run at the fabric's gather rate, where a wave that waits in its
+// epilogue is one wave less gathering; grouped, its waves waited 20 % of their cycles instead of 44 % and the launch took 4 % LONGER
+// (0.650 -> 0.678 ms plain, 0.901 -> 0.921 Adam, 0.746 -> 0.788 layer sum; profiles/blocked_epilogue.md).
+template <int UNR, bool MASKED> constexpr bool kEpiGrouped = MASKED || UNR == 16;
+// Output rows per group.  Two groups' loaded values are live at once (the next group's loads are issued before this group's stores):
+// 2 * K * kEpiLoads * CPL registers, which have to fit in what the gather loop frees -- its staging x[16], or the masked loop's three
+// stages -- so that no build needs more registers than its gather loop does (8 waves per SIMD at 16 loads in flight, 7 masked).
+template <int MODE, bool MASKED> constexpr int kEpiGroup = MODE == EPI_ADAM ? 2 : MASKED ? 8 : 4;
 
 // MASKED (the first backward hop: X = the batch gradient, non-zero on <= 3B rows whose bits are set in P.xbits): every lane tests the bit of
 // its own record's column, one ballot gives the batch's hits, and only those are gathered -- kMaskedUnr loads first, then their FMAs, in
@@ -771,6 +886,9 @@ __global__ __launch_bounds__(kBlock) void spmm_blocked64_kernel(BlockedDev P, co
 #pragma unroll
         for (int r = 0; r < 32; ++r) acc[c][r] = 0.f;
     const int begin = P.wave_ptr[w], end = P.wave_ptr[w + 1];
+    constexpr bool GROUPED = kEpiGrouped<UNR, MASKED>;
+    int my_row = -1;                                             // slot `lane`'s output row; in flight under the first record batch
+    if (GROUPED && lane < RPW) my_row = P.wave_rows[(size_t)w * RPW + lane];
     const float *xl = X + lane * CPL;
     if (MASKED) {
         // three stages in flight per wave: the records of batch b + 2, the bitmap words of batch b + 1, the gathers of batch b
@@ -832,18 +950,70 @@ __global__ __launch_bounds__(kBlock) void spmm_blocked64_kernel(BlockedDev P, co
         }
     }
     }
-#pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-        const int row = P.wave_rows[w * RPW + r];
-        float a[CPL];
-#pragma unroll
-        for (int c = 0; c < CPL; ++c) a[c] = acc[c][r];
-        if (row >= 0) spmm_epilogue1<MODE, CPL, LD>(ep, row, lane, a);
+    auto row_epilogue = [&](int row, bool zr, float rs, const float *a) {
+        if (row >= 0) spmm_epilogue1<MODE, CPL, LD>(ep, row, zr, rs, lane, a);
         else if (row < -1) {                                     // piece of a split (hub) row: raw sum, combined by spmm_long_rows_kernel
             float *dst = P.partial + ((size_t)(-row - 2) * 64 + lane) * CPL;
 #pragma unroll
             for (int c = 0; c < CPL; ++c) dst[c] = a[c];
         }
+    };
+    if constexpr (!GROUPED) {                                    // row at a time: id, flag, scale, Z / S_in / P, M, V, each waited for, then the stores
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) {
+            const int row = P.wave_rows[w * RPW + r];
+            float a[CPL];
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) a[c] = acc[c][r];
+            const bool zr = row >= 0 && MODE != EPI_LAYERSUM && ep.Z && (!ep.zflags || ep.zflags[row]);
+            const float rs = (row >= 0 && MODE == EPI_AXPBY && ep.rscale) ? ep.rscale[row] : 0.f;
+            row_epilogue(row, zr, rs, a);
+        }
+    } else {
+    // Grouped.  Lane r holds slot r's row id (loaded at entry), its Z flag and its row scale -- one load each per wave -- and the row
+    // loops read them with v_readlane.  The slots before the wave's first padding slot go in groups of K: the loads of group g + 1 are
+    // issued before the stores of group g and nothing is loaded between two stores, so the wave waits for a group's loads, never for
+    // a store's acknowledgement (nothing here is `restrict`; row at a time, every load waits for the previous row's store, four waits
+    // per row).  Rows of one wave are distinct: reading a row's Z / S_in / P / M / V ahead of another row's stores reads the same
+    // values, in place or not.  The plan fills a wave's slots from 0, so the row-at-a-time rest is the last group of a padded wave.
+    bool my_zr = false; float my_rs = 0.f;
+    if (my_row >= 0) {
+        if (MODE == EPI_AXPBY && ep.rscale) my_rs = ep.rscale[my_row];
+        if (MODE != EPI_LAYERSUM) my_zr = ep.Z && (!ep.zflags || ep.zflags[my_row]);
+    }
+    const unsigned zmask = (unsigned)__ballot(my_zr);
+    const unsigned long long rows = __ballot(my_row >= 0), pads = __ballot(my_row == -1);     // lanes >= RPW count as padding: pads != 0
+    constexpr int K = kEpiGroup<MODE, MASKED>, NG = RPW / K;
+    static_assert(RPW % K == 0, "whole groups");
+    const int n_grouped = rows ? __builtin_ctzll(pads) / K : 0;       // `safe_row` needs one row of the wave's own
+    if (n_grouped > 0) {
+        const int safe_row = __builtin_amdgcn_readlane(my_row, __builtin_ctzll(rows));
+        float in[2][K][kEpiLoads<MODE>][CPL];
+        spmm_group_load<MODE, K, CPL, LD>(ep, my_row, zmask, safe_row, 0, lane, in[0]);
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            // also for a group that is left to the loop below: every address is valid, and leaving is the only branch on this path
+            if (g + 1 < NG) spmm_group_load<MODE, K, CPL, LD>(ep, my_row, zmask, safe_row, (g + 1) * K, lane, in[(g + 1) & 1]);
+            float a[K][CPL], out[K][kEpiStores<MODE>][CPL];
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                const int r = g * K + i;
+#pragma unroll
+                for (int c = 0; c < CPL; ++c) a[i][c] = acc[c][r];
+                const float rs = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(my_rs), r));
+                spmm_epilogue_math<MODE, CPL>(ep, (zmask >> r) & 1u, rs, a[i], in[g & 1][i], out[i]);
+            }
+            spmm_group_store<MODE, K, CPL, LD>(ep, P.partial, my_row, g * K, lane, a, out);
+            if (g + 1 == n_grouped) break;
+        }
+    }
+#pragma nounroll
+    for (int r = n_grouped * K; r < RPW; ++r) {
+        float a[CPL];
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) a[c] = acc[c][r];
+        row_epilogue(__builtin_amdgcn_readlane(my_row, r), (zmask >> r) & 1u, __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(my_rs), r)), a);
+    }
     }
 }
 
