@@ -128,6 +128,8 @@ _SIGS = {
     'arl_gan_threshold_f32': (C.c_int, [_vp, _i64, _i64, _f, _vp, _vp, _vp, _vp]),
     'arl_colsoftmax_target_workspace_bytes': (_i64, [_i64, _i64, _i64, _i32]),
     'arl_colsoftmax_target_loss_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'arl_bce_allpairs_workspace_bytes': (_i64, [_i64, _i64, _i64, _i32]),
+    'arl_bce_allpairs_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     'arl_kmeans_assign_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     'arl_kmeans_chunk_rows': (_i64, []),
     'arl_kmeans_update_workspace_bytes': (_i64, [_i64, _i64, _i64]),

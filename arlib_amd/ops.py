@@ -1917,3 +1917,8 @@ def gan_threshold(Y, thr=0.1):
 # ================================================================================================ LegUP's ranking loss (csrc/arl_colsoftmax.hip)
 # (module of its own: arlib_amd/colsoftmax.py, with its poisoned-memory sweep in tests/test_gpu_legup_poison.py)
 from .colsoftmax import colsoftmax_target_supported, colsoftmax_target_loss, colsoftmax_target_loss_composed, colsoftmax_target  # noqa: E402,F401
+
+# ================================================================================================ GSPAttack's all-pairs BCE (csrc/arl_allpairs.hip)
+# (module of its own: arlib_amd/allpairs.py, with its poisoned-memory runs in tests/test_gpu_gsp_poison.py)
+from .allpairs import (ALLPAIRS_WIDTHS, ALLPAIRS_MAX_ROWS, bce_allpairs_supported, batch_mean_row_weights, transpose_positives,  # noqa: E402,F401
+                       bce_allpairs_loss, bce_allpairs_loss_composed, bce_allpairs)

@@ -615,6 +615,26 @@ int arl_colsoftmax_target_loss_f32(const float *Pu, int64_t U, const float *Pi, 
                                    float *loss, float *dPu, float *dPi, void *workspace, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * GSPAttack's L_per (csrc/arl_allpairs.hip; reference attack/Black/GSPAttack.py:63-75) -- a binary cross-entropy over every score of
+ * s = Pu Pi^T [R, I], which is never stored, against a sparse target matrix.  Pu [R, d], Pi [I, d], d in {16, 32, 64, 128}, 16-byte aligned,
+ * rows of either table <= (2^31 - 1) / 128.  With f0(s) = -log(sigmoid(-s) + eps), f1(s) = -log(sigmoid(s) + eps):
+ *   pos_rowptr [R + 1], pos_col [nnz], pos_val [nnz] | NULL (all 1): the positives (r, c) with weights a, CSR by row, int32; a repeated
+ *     entry counts as often as it is listed.  post_rowptr [I + 1], post_col [nnz] (row ids), post_perm [nnz] | NULL: the same set by item,
+ *     post_perm mapping its entries to pos_val (needed with pos_val); read only when dPi is wanted.
+ *   rowloss [R] : sum_i f0(s[r, i]) + sum_{(r, c) listed} a (f1 - f0)(s[r, c])          (unweighted)
+ *   loss [1]    : sum_r row_weight[r] rowloss[r]                                        (accumulated in double)
+ *   dPu [R, d], dPi [I, d] (each optional, NULL = skipped): gradients of upstream * loss.
+ * Fixed-order reductions, no atomics: bit-identical from run to run, and the loss-only call gives the bits of the gradient call.  The
+ * workspace (arl_bce_allpairs_workspace_bytes; 0 for a shape outside the limits) needs no initialisation. */
+/* attack/Black/GSPAttack.py:63-75 */
+int64_t arl_bce_allpairs_workspace_bytes(int64_t R, int64_t I, int64_t d, int32_t want_grad);
+/* attack/Black/GSPAttack.py:63-75 */
+int arl_bce_allpairs_f32(const float *Pu, int64_t R, const float *Pi, int64_t I, int64_t d, const int32_t *pos_rowptr, const int32_t *pos_col,
+                         const float *pos_val, const int32_t *post_rowptr, const int32_t *post_col, const int32_t *post_perm,
+                         const float *row_weight, float eps, float upstream, float *rowloss, float *loss, float *dPu, float *dPi, void *workspace,
+                         arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Lloyd's k-means for NCL's prototypes (csrc/arl_kmeans.hip).  Replaces recommender/NCL.py:52-73 (e_step / run_kmeans: sklearn's KMeans on
  * host copies of the tables; the commented faiss.Kmeans(gpu=True) of :61-66 is what the authors meant).  X [N, d] points, C [k, d]
  * centroids, d in {16, 32, 64, 128} (else ARL_E_DIM), N, k >= 1 (else ARL_E_ARG) and <= 2^31 / 128 (else ARL_E_RANGE), X, C and
