@@ -130,7 +130,14 @@ _SIGS = {
     'arl_colsoftmax_target_loss_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'arl_bce_allpairs_workspace_bytes': (_i64, [_i64, _i64, _i64, _i32]),
     'arl_bce_allpairs_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'arl_kmeans_assign_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'arl_pair_mlp_fwd_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'arl_pair_mlp_workspace_bytes': (_i64, [_i64, _i64, _i64]),
+    'arl_pair_mlp_bwd_f32': (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'arl_gumbel_topk_workspace_bytes': (_i64, [_i64, _i64, _i64, _i32]),
+    'arl_gumbel_topk_fwd_f32': (C.c_int, [_vp, _i64, _i64, _i64, _f, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'arl_gumbel_topk_bwd_f32': (C.c_int, [_vp, _i64, _i64, _i64, _f, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'arl_gumbel_noise_f32': (C.c_int, [C.c_uint64, C.c_uint64, _i64, _i64, _i64, _vp, _vp]),
+    'arl_kmeans_assign_f32':(C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     'arl_kmeans_chunk_rows': (_i64, []),
     'arl_kmeans_update_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'arl_kmeans_update_f32': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),

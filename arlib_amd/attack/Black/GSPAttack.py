@@ -20,8 +20,16 @@ Mechanics: the real users' part of L_per (a binary cross-entropy over all U x I 
 through ops.bce_allpairs (csrc/arl_allpairs.hip) with the reference's batched-mean weights (ops.batch_mean_row_weights); the fake users' F x I panel,
 L_exPR and the MLP are plain torch.  The hop reuses PGA's FactoredFakeGraph and ops.sddmm_rows_dense, a layer is ops.ngcf_dense_fwd / _bwd.  The dense
 F x I block is the size limit, as in PGA.
+
+The profile generator has two routes (attribute profile_route, set on the instance before posionDataAttack): 'composed', the default, is the MLP
+one fake user at a time and gumbel_topk_relaxed, both plain torch; 'fused' forms the first layer's two halves with two GEMMs and runs
+ops.pair_mlp_logits_auto and ops.gumbel_topk_auto (csrc/arl_profilegen.hip; the composed routes past the kernels' limits).  noise_source 'torch'
+(the default) draws self._noise((k, F, I)) on both routes; 'hash' draws one seed per attack from Python's random and takes the noise from a counter
+hash of (seed, epoch, round, fake user, item): the fused route regenerates it inside the kernels, so no [k, F, I] tensor exists (the composed
+route writes the same draw out with ops.gumbel_noise).
 """
 import math
+import random
 
 import numpy as np
 import scipy.sparse as sp
@@ -179,6 +187,14 @@ class NGCFProxy(nn.Module):
             return self.mlp(torch.cat([u_row.expand(self.item_num, -1), Pi_prev], 1))[:, 0]
         return torch.stack([checkpoint(one, Pu_prev[self.user_num + f], use_reentrant=False) for f in range(self.fakeUserNum)], 0)
 
+    def pair_logits_fused(self, Pu_prev, Pi_prev):
+        """The same x [F, I] with the first layer split over its two inputs: A = E_f W1[:, :d]^T + b1 and B = E_i W1[:, d:]^T stay torch GEMMs (autograd
+        carries the gradient to W1 and b1), the ReLU and the second layer over every pair run in ops.pair_mlp_logits_auto."""
+        lin1, lin2, d = self.mlp.net[0], self.mlp.net[2], self.latent_size
+        A = Pu_prev[self.user_num:] @ lin1.weight[:, :d].t() + lin1.bias
+        B = Pi_prev @ lin1.weight[:, d:].t()
+        return ops.pair_mlp_logits_auto(A, B, lin2.weight[0], lin2.bias)
+
 
 class GSPAttack(AttackBase):
     recommenderGradientRequired = False
@@ -203,6 +219,8 @@ class GSPAttack(AttackBase):
         self.loss_log = []
         self.pick_log = []                 # the k picks per fake user of every epoch's Gumbel top-k
         self.first_dS = None               # dLoss/dS of the first epoch
+        self.profile_route = 'composed'    # 'composed': the MLP per fake user and the Gumbel rounds in torch; 'fused': csrc/arl_profilegen.hip
+        self.noise_source = 'torch'        # 'torch': self._noise((k, F, I)); 'hash': a counter hash of one seed per attack
 
     def _noise(self, shape):
         """Gumbel noise [k, F, I] on the device, drawn as F.gumbel_softmax draws it; a test replaces this method."""
@@ -235,6 +253,12 @@ class GSPAttack(AttackBase):
 
     def posionDataAttack(self):
         U, F, I, k = self.userNum, self.fakeUserNum, self.itemNum, self.maliciousFeedbackNum
+        if self.profile_route not in ('composed', 'fused'):
+            raise ValueError("GSPAttack: profile_route is 'composed' or 'fused', not %r" % (self.profile_route,))
+        if self.noise_source not in ('torch', 'hash'):
+            raise ValueError("GSPAttack: noise_source is 'torch' or 'hash', not %r" % (self.noise_source,))
+        fused = self.profile_route == 'fused'
+        hash_seed = random.getrandbits(63) if self.noise_source == 'hash' else None
         if self.ngcf is None:
             self.ngcf = self._proxy()
         ngcf = self.ngcf
@@ -243,8 +267,15 @@ class GSPAttack(AttackBase):
         with torch.no_grad():
             Pu_prev, Pi_prev = ngcf(torch.full((F, I), S_INIT, dtype=torch.float32, device=DEVICE))
         for epoch in range(self.Epoch):
-            x = ngcf.pair_logits(Pu_prev, Pi_prev)
-            S, picks = gumbel_topk_relaxed(x, k, noise=self._noise((k, F, I)))
+            if not fused:
+                x = ngcf.pair_logits(Pu_prev, Pi_prev)
+                S, picks = gumbel_topk_relaxed(x, k, noise=self._noise((k, F, I)) if hash_seed is None else ops.gumbel_noise(hash_seed, epoch, k, F, I, DEVICE))
+            else:
+                x = ngcf.pair_logits_fused(Pu_prev, Pi_prev)
+                if hash_seed is None:
+                    S, picks = ops.gumbel_topk_auto(x, k, noise=self._noise((k, F, I)))
+                else:
+                    S, picks = ops.gumbel_topk_auto(x, k, seed=hash_seed, call=epoch)
             if epoch == 0:
                 S.retain_grad()
             Loss, Pu, Pi = self.epoch_loss(ngcf, S)

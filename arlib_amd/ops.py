@@ -1922,3 +1922,9 @@ from .colsoftmax import colsoftmax_target_supported, colsoftmax_target_loss, col
 # (module of its own: arlib_amd/allpairs.py, with its poisoned-memory runs in tests/test_gpu_gsp_poison.py)
 from .allpairs import (ALLPAIRS_WIDTHS, ALLPAIRS_MAX_ROWS, bce_allpairs_supported, batch_mean_row_weights, transpose_positives,  # noqa: E402,F401
                        bce_allpairs_loss, bce_allpairs_loss_composed, bce_allpairs)
+
+# ================================================================================================ GSPAttack's profile generator (csrc/arl_profilegen.hip)
+# (module of its own: arlib_amd/profilegen.py, with its poisoned-memory runs in tests/test_gpu_profilegen_poison.py)
+from .profilegen import (PAIR_MLP_MAX_H, GUMBEL_MAX_K, pair_mlp_supported, gumbel_topk_supported, pair_mlp_fwd, pair_mlp_bwd, pair_mlp_logits,  # noqa: E402,F401
+                         pair_mlp_logits_composed, pair_mlp_logits_auto, gumbel_noise, gumbel_topk_fwd, gumbel_topk_bwd, gumbel_topk,
+                         gumbel_topk_composed, gumbel_topk_auto)

@@ -635,6 +635,43 @@ int arl_bce_allpairs_f32(const float *Pu, int64_t R, const float *Pi, int64_t I,
                          arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * GSPAttack's profile generator (csrc/arl_profilegen.hip; reference attack/Black/GSPAttack.py:120-130, 201-202, 224-231 as repaired in
+ * arlib_amd/attack/Black/GSPAttack.py).  Every pointer 16-byte aligned; ARL_E_DIM for H > 1024 or k > 512, ARL_E_RANGE for F or I outside
+ * the kernels' grids (F <= 524 280 for the pair MLP, I <= 2^31 - 2049, F * ceil(I / 256) [* k for the noise] < 2^31), ARL_E_ARG for an
+ * empty or misaligned argument, k > I or tau <= 0; all checked before any launch.  No atomics, fixed-order reductions: bit-identical from
+ * run to run.  No workspace needs initialisation.
+ *
+ * Pair-MLP head: A [F, H], B [I, H], w2 [H], b2 [1] (device) -> x [F, I], x[f, i] = b2 + sum_h w2[h] relu(A[f, h] + B[i, h]); the
+ * Linear(2d, H) - ReLU - Linear(H, 1) of the reference on cat(e_f, e_i) with A = E_f W1[:, :d]^T + b1 and B = E_i W1[:, d:]^T.  No
+ * F x I x H tensor exists.  Backward for an upstream g [F, I] (the ReLU derivative at exactly 0 is 0):
+ *   dA[f, h] = w2[h] sum_i g[f, i] [A[f, h] + B[i, h] > 0],   dB[i, h] = w2[h] sum_f g[f, i] [A[f, h] + B[i, h] > 0],
+ *   dw2[h] = sum_{f, i} g[f, i] relu(A[f, h] + B[i, h]),      db2 [1] = sum g;       sums in fp32 per tile, in double across tiles. */
+/* attack/Black/GSPAttack.py:120-130 */
+int arl_pair_mlp_fwd_f32(const float *A, int64_t F, const float *B, int64_t I, int64_t H, const float *w2, const float *b2, float *x, arl_stream_t stream);
+/* attack/Black/GSPAttack.py:120-130 */
+int64_t arl_pair_mlp_workspace_bytes(int64_t F, int64_t I, int64_t H);
+/* attack/Black/GSPAttack.py:120-130 */
+int arl_pair_mlp_bwd_f32(const float *g, const float *A, int64_t F, const float *B, int64_t I, int64_t H, const float *w2, float *dA, float *dB, float *dw2,
+                         float *db2, void *workspace, arl_stream_t stream);
+/* Relaxed Gumbel top-k: x [F, I] finite, 1 <= k <= I, tau > 0.  Round r, over the items not picked in earlier rounds: z = (x + g_r) / tau,
+ * y_r = softmax(z) over the items, j_r = argmax z (the lowest index on an exact tie).
+ *   S [F, I] = sum_r y_r,  picks [F, k] int32,  lse [F, k] the per-round log-sum-exp,  stats [F, k, 2] the per-round (max z, sum exp(z - max)).
+ * noise [k, F, I] is the caller's g; NULL: g = -log(-log u), u in (0, 1) from 24 bits of a splitmix64 counter hash of
+ * (seed, call, r, f, i) -- a function of those five numbers only.  arl_gumbel_noise_f32 writes that draw out as [k, F, I].
+ * Backward (the argmax detached): dx[f, i] = (1 / tau) sum_r y_r[i] (dS[f, i] - sum_j y_r[j] dS[f, j]), y_r recomputed from x, the noise,
+ * picks and stats.  Workspace: forward F * ceil(I / 32) words, backward F * ceil(I / 256) * k + F * k floats. */
+/* attack/Black/GSPAttack.py:201-202, 224-231 */
+int64_t arl_gumbel_topk_workspace_bytes(int64_t F, int64_t I, int64_t k, int32_t backward);
+/* attack/Black/GSPAttack.py:201-202, 224-231 */
+int arl_gumbel_topk_fwd_f32(const float *x, int64_t F, int64_t I, int64_t k, float tau, const float *noise, uint64_t seed, uint64_t call, float *S, int32_t *picks,
+                            float *lse, float *stats, void *workspace, arl_stream_t stream);
+/* attack/Black/GSPAttack.py:201-202, 224-231 */
+int arl_gumbel_topk_bwd_f32(const float *x, int64_t F, int64_t I, int64_t k, float tau, const float *noise, uint64_t seed, uint64_t call, const int32_t *picks,
+                            const float *stats, const float *dS, float *dx, void *workspace, arl_stream_t stream);
+/* attack/Black/GSPAttack.py:201-202, 224-231 */
+int arl_gumbel_noise_f32(uint64_t seed, uint64_t call, int64_t k, int64_t F, int64_t I, float *out, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Lloyd's k-means for NCL's prototypes (csrc/arl_kmeans.hip).  Replaces recommender/NCL.py:52-73 (e_step / run_kmeans: sklearn's KMeans on
  * host copies of the tables; the commented faiss.Kmeans(gpu=True) of :61-66 is what the authors meant).  X [N, d] points, C [k, d]
  * centroids, d in {16, 32, 64, 128} (else ARL_E_DIM), N, k >= 1 (else ARL_E_ARG) and <= 2^31 / 128 (else ARL_E_RANGE), X, C and

@@ -3,7 +3,11 @@
 backward, at cfg2's shape (SYN-v1 1 M x 100 K, d 64, nnz 32 095 419) and at ml-1M's shape (6 040 x 3 706, nnz 1 000 209).  The positives are drawn
 uniformly (the loss's cost does not depend on where they lie).  Prints one JSON line per shape.
 
-    python tools/gsp_bench.py [--shape cfg2|ml1m|both --dim 64 --reps 3 --composed-rows 20000]
+    python tools/gsp_bench.py [--shape cfg2|ml1m|both|none --dim 64 --reps 3 --composed-rows 20000] [--generator ml1m|cfg2|big|all]
+
+--generator adds the profile generator's legs (pair-MLP logits + relaxed Gumbel top-k, forward + backward, csrc/arl_profilegen.hip): the fused and
+the composed route in the same run at ml-1M's default budget (F 60, I 3 706, k 165, H 60) and at cfg2 with the bench's block of fake users (F 64,
+I 100 000, k 32, H 316), and the fused route alone with hash noise at cfg2's default budget (F 10 000), with its peak memory.
 
 The composed route at cfg2's size takes minutes (7 813 panels of 128 x 100 000 scores), so it is timed on the first --composed-rows rows and scaled
 linearly in R (its cost per panel does not depend on R)."""
@@ -66,15 +70,71 @@ def run(name, d, reps, composed_rows):
     print(json.dumps(out), flush=True)
 
 
+GEN_SHAPES = {'ml1m': dict(F=60, I=3706, k=165, H=60), 'cfg2': dict(F=64, I=100_000, k=32, H=316), 'big': dict(F=10_000, I=100_000, k=32, H=316)}
+
+
+def run_generator(name, d, reps):
+    from torch.utils.checkpoint import checkpoint
+    from arlib_amd.attack.Black.GSPAttack import MLP, gumbel_topk_relaxed
+    F, I, k, H = (GEN_SHAPES[name][n] for n in 'FIkH')
+    g = torch.Generator(device='cuda').manual_seed(0)
+    Ef, Ei = torch.randn(F, d, device='cuda', generator=g) * 0.1, torch.randn(I, d, device='cuda', generator=g) * 0.1
+    torch.manual_seed(0)
+    mlp = MLP(2 * d, H).cuda()
+    lin1, lin2 = mlp.net[0], mlp.net[2]
+    up = torch.randn(F, I, device='cuda', generator=g)
+    out = dict(leg='generator', shape=name, fake_users=F, items=I, k=k, hidden=H, dim=d)
+
+    def fused(**src):
+        mlp.zero_grad(set_to_none=True)
+        A = Ef @ lin1.weight[:, :d].t() + lin1.bias
+        B = Ei @ lin1.weight[:, d:].t()
+        S, _ = ops.gumbel_topk(ops.pair_mlp_logits(A, B, lin2.weight[0], lin2.bias), k, **src)
+        S.backward(up)
+
+    def composed(noise):
+        mlp.zero_grad(set_to_none=True)
+        one = lambda u_row: mlp(torch.cat([u_row.expand(I, -1), Ei], 1))[:, 0]
+        x = torch.stack([checkpoint(one, Ef[f], use_reentrant=False) for f in range(F)], 0)
+        S, _ = gumbel_topk_relaxed(x, k, noise=noise)
+        S.backward(up)
+    if name == 'big':
+        torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out['fused_hash_fwd_bwd_s'] = timed(lambda: fused(seed=1, call=0), 1)
+        out['fused_hash_peak_bytes'] = torch.cuda.max_memory_allocated() - base
+        out['composed_noise_and_softmax_bytes'] = 2 * k * F * I * 4
+    else:
+        noise = -torch.empty(k, F, I, device='cuda').exponential_(generator=g).log()
+        out['fused_fwd_bwd_s'] = timed(lambda: fused(noise=noise), reps)
+        out['fused_hash_fwd_bwd_s'] = timed(lambda: fused(seed=1, call=0), reps)
+        out['composed_fwd_bwd_s'] = timed(lambda: composed(noise), reps)
+        out['speedup_fwd_bwd'] = out['composed_fwd_bwd_s'] / out['fused_fwd_bwd_s']
+        A = (Ef @ lin1.weight[:, :d].t() + lin1.bias).detach()
+        B = (Ei @ lin1.weight[:, d:].t()).detach()
+        w2, b2 = lin2.weight[0].detach(), lin2.bias.detach()
+        x = ops.pair_mlp_fwd(A, B, w2, b2)
+        out['pair_mlp_fwd_s'] = timed(lambda: ops.pair_mlp_fwd(A, B, w2, b2), reps)
+        out['pair_mlp_bwd_s'] = timed(lambda: ops.pair_mlp_bwd(up, A, B, w2, b2), reps)
+        _, picks, _, stats = ops.gumbel_topk_fwd(x, k, noise=noise)
+        out['gumbel_fwd_s'] = timed(lambda: ops.gumbel_topk_fwd(x, k, noise=noise), reps)
+        out['gumbel_bwd_s'] = timed(lambda: ops.gumbel_topk_bwd(up, x, k, picks, stats, noise=noise), reps)
+        out['gumbel_hash_fwd_s'] = timed(lambda: ops.gumbel_topk_fwd(x, k, seed=1), reps)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--shape', choices=('cfg2', 'ml1m', 'both'), default='both')
+    ap.add_argument('--shape', choices=('cfg2', 'ml1m', 'both', 'none'), default='both')
+    ap.add_argument('--generator', choices=('none', 'ml1m', 'cfg2', 'big', 'all'), default='none')
     ap.add_argument('--dim', type=int, default=64)
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--composed-rows', type=int, default=20000)
     a = ap.parse_args()
-    for name in (('ml1m', 'cfg2') if a.shape == 'both' else (a.shape,)):
+    for name in (('ml1m', 'cfg2') if a.shape == 'both' else () if a.shape == 'none' else (a.shape,)):
         run(name, a.dim, a.reps, a.composed_rows)
+    for name in (('ml1m', 'cfg2', 'big') if a.generator == 'all' else () if a.generator == 'none' else (a.generator,)):
+        run_generator(name, a.dim, a.reps)
 
 
 if __name__ == '__main__':
