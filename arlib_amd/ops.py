@@ -1928,3 +1928,9 @@ from .allpairs import (ALLPAIRS_WIDTHS, ALLPAIRS_MAX_ROWS, bce_allpairs_supporte
 from .profilegen import (PAIR_MLP_MAX_H, GUMBEL_MAX_K, pair_mlp_supported, gumbel_topk_supported, pair_mlp_fwd, pair_mlp_bwd, pair_mlp_logits,  # noqa: E402,F401
                          pair_mlp_logits_composed, pair_mlp_logits_auto, gumbel_noise, gumbel_topk_fwd, gumbel_topk_bwd, gumbel_topk,
                          gumbel_topk_composed, gumbel_topk_auto)
+
+# ================================================================================================ PoisonRec's policy head (csrc/arl_policyhead.hip)
+# (module of its own: arlib_amd/policyhead.py, with its poisoned-memory runs in tests/test_gpu_policyhead_poison.py)
+from .policyhead import (POLICYHEAD_WIDTHS, POLICYHEAD_MAX_ROWS, bernoulli_softmax_supported, pack_bits, unpack_bits, bernoulli_softmax_eval,  # noqa: E402,F401
+                         bernoulli_softmax_eval_composed, bernoulli_softmax, bernoulli_softmax_head, bernoulli_uniforms, bernoulli_softmax_sample,
+                         bernoulli_softmax_sample_composed, bernoulli_softmax_sample_auto)

@@ -672,6 +672,31 @@ int arl_gumbel_topk_bwd_f32(const float *x, int64_t F, int64_t I, int64_t k, flo
 int arl_gumbel_noise_f32(uint64_t seed, uint64_t call, int64_t k, int64_t F, int64_t I, float *out, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PoisonRec's policy head (csrc/arl_policyhead.hip; reference attack/Black/PoisonRec.py:363-371, 398-401) -- a Bernoulli distribution over
+ * every item whose logits are p = softmax_i(q E^T), with no B x I tensor.  q [B, d], E [I, d] fp32, d in {16, 32, 64, 128} (else ARL_E_DIM),
+ * 16-byte aligned, B, I >= 1 (else ARL_E_ARG) and <= (2^31 - 1) / 128 (else ARL_E_RANGE).  actions [B, W] int32, W = ceil(I / 32): bit i % 32
+ * of word i / 32 is item i; pad bits are written as 0 and never read as items.  With sp = softplus(p), sg = sigmoid(p):
+ *   logp [B] = sum_i (a p - sp),   ent [B] = sum_i (sp - p sg)
+ *   dq [B, d], dE [I, d] (each optional, NULL = skipped; gl [B], ge [B] are then required): the gradients of sum_b gl[b] logp[b] + ge[b] ent[b],
+ *     dz_i = p_i (c_i - sum_j p_j c_j) with c_i = gl (a_i - sg_i) - ge p_i sg_i (1 - sg_i), dq = dz E, dE = dz^T q.
+ * eval: four streamed passes (row max and sum, row sums, dq, dE).  sample: the first pass, then a_i = (u_i < sg_i) with u the caller's
+ * [B, I] tensor or, u NULL, u = n 2^-24 from 24 bits of the splitmix64 counter hash of (seed, call, row0 + b, i); deterministic != 0:
+ * a_i = (p_i > 0), which is sg_i > 1/2.  It writes the packed actions, logp and count [B] (the set bits per row).
+ * arl_bernoulli_uniforms_f32 writes the hash's draw out as [B, I].  No atomics, fixed-order reductions: bit-identical from run to run.
+ * The workspace (arl_bernoulli_softmax_workspace_bytes, want_grad = 1 when dq or dE is asked for; 0 for a shape outside the limits) needs
+ * no initialisation. */
+/* attack/Black/PoisonRec.py:363-371, 398-401 */
+int64_t arl_bernoulli_softmax_workspace_bytes(int64_t B, int64_t I, int64_t d, int32_t want_grad);
+/* attack/Black/PoisonRec.py:363-371, 398-401 */
+int arl_bernoulli_softmax_eval_f32(const float *q, int64_t B, const float *E, int64_t I, int64_t d, const int32_t *actions, const float *gl, const float *ge,
+                                   float *logp, float *ent, float *dq, float *dE, void *workspace, arl_stream_t stream);
+/* attack/Black/PoisonRec.py:363-371, 398-401 */
+int arl_bernoulli_softmax_sample_f32(const float *q, int64_t B, const float *E, int64_t I, int64_t d, const float *u, uint64_t seed, uint64_t call, int64_t row0,
+                                     int32_t deterministic, int32_t *actions, float *logp, int32_t *count, void *workspace, arl_stream_t stream);
+/* attack/Black/PoisonRec.py:363-371, 398-401 */
+int arl_bernoulli_uniforms_f32(uint64_t seed, uint64_t call, int64_t row0, int64_t B, int64_t I, float *out, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Lloyd's k-means for NCL's prototypes (csrc/arl_kmeans.hip).  Replaces recommender/NCL.py:52-73 (e_step / run_kmeans: sklearn's KMeans on
  * host copies of the tables; the commented faiss.Kmeans(gpu=True) of :61-66 is what the authors meant).  X [N, d] points, C [k, d]
  * centroids, d in {16, 32, 64, 128} (else ARL_E_DIM), N, k >= 1 (else ARL_E_ARG) and <= 2^31 / 128 (else ARL_E_RANGE), X, C and
