@@ -90,6 +90,8 @@ _SIGS = {
     'arl_ncf_tower_bwd_f32': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'arl_wrmf_l2_workspace_bytes': (_i64, [_i64]),
     'arl_wrmf_l2_fwd_bwd_f32': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _f, _f, _f, _vp, _vp, _vp, _i32, _vp]),
+    'arl_bpr_adv_workspace_bytes': (_i64, [_i64, _i64]),
+    'arl_bpr_adv_fwd_bwd_f32': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp, _i32, _vp]),
     'arl_sfa_workspace_bytes': (_i64, [_i64, _i64]),
     'arl_sfa_l1_fwd_bwd_f32': (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _f, C.c_int32, _vp, _vp, _vp, _vp]),
     'arl_sfa_stage1_f32': (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),

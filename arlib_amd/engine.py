@@ -86,6 +86,7 @@ class PropagationEngine:
         self._sparse_B, self._sb_cache = None, {}
         self.Gc = self.out_c = self.rows_ws = self.ar = self.arB = self._ws = None                 # batch-sized, _sparse_buffers()
         self._sgl_acc = self._sgl_hops = None       # step_sgl()
+        self._apr_ws = {}                           # step_apr(): the adversarial kernel's workspace per batch size
         self.ngcf_W = self.ngcf_m = self.ngcf_v = None      # init_ngcf()
 
     # views with the reference's names
@@ -329,6 +330,32 @@ class PropagationEngine:
         self._step_sparse(u, p, n, None, contrastive)
         cl = cl[0]
         return self.loss_out, cl_rate * (cl[1] + cl[0])
+
+    def step_apr(self, u, p, n, eps=0.5, adv_reg=1.0):
+        """One APR training iteration (Adversarial Personalized Ranking, He et al., SIGIR'18): the step() schedule plus ONE call of the
+        adversarial-BPR kernel (ops.bpr_adv_fwd_bwd), which perturbs the rows the scorer reads by eps * l2_normalize(their BPR gradient, summed
+        per node) and adds adv_reg * the gradient of BPR on the perturbed rows.  Sparse form: the kernel reads the compact propagated batch
+        rows out_c and adds into the compact gradient Gc before it enters G -- no extra hop.  Dense form (L = 0: APR as published; SGD,
+        skip_layer0, L > 8): step_dense with the kernel adding into G after the BPR kernel.  The L2 term stays on the clean rows.
+        Returns (loss_out, adv_loss) device tensors (no host sync); loss = loss_out[0] + loss_out[1] + adv_reg * adv_loss."""
+        B = u.numel()
+        if not ops.bpr_adv_supported(B, self.d):
+            raise ValueError('step_apr: batch size %d, embedding size %d unsupported (B <= %d, d <= %d)' % (B, self.d, ops.BPR_ADV_MAX_BATCH, ops.BPR_ADV_MAX_WIDTH))
+        adv = torch.empty(2, dtype=torch.float32, device=self.device)
+        ws = self._apr_ws.get(B)
+        if ws is None:
+            if len(self._apr_ws) >= 8:
+                del self._apr_ws[next(iter(self._apr_ws))]
+            ws = self._apr_ws[B] = torch.empty(ops._lib.lib().arl_bpr_adv_workspace_bytes(B, self.d) // 4, dtype=torch.float32, device=self.device)
+        if self.optimizer != 'adam' or self.L == 0 or self.skip0 or self.L > 8:
+            def adversarial(out):
+                ops.bpr_adv_fwd_bwd(out, self.U, u, p, n, eps, G=self.G, upstream=adv_reg, workspace=ws, loss_out=adv, check_range=False)
+            return self.step_dense(u, p, n, adversarial), adv_reg * adv[0]
+        rows = self._batch_rows(u, p, n)
+        def adversarial():
+            ops.bpr_adv_fwd_bwd(self.out_c, B, self.ar, self.ar, self.arB, eps, groups=rows, G=self.Gc, upstream=adv_reg, workspace=ws, loss_out=adv,
+                                check_range=False, distinct_rows=True)
+        return self._step_sparse(u, p, n, rows, adversarial), adv_reg * adv[0]
 
     # ---- NGCF (recommender/NGCF.py:47-64,197-212): the whole training iteration without autograd or a torch optimizer.  Per layer ONE hop
     # P = A E (A(E W1) = (A E) W1) and the fp32-MFMA dense part (ops.ngcf_dense_*); sparse-batch schedule as in step(): the LAST layer is
@@ -625,11 +652,14 @@ class PropagationEngine:
         self.Gc, self.out_c, self.rows_ws, self.ar, self.arB, self._ws = sb
         self._sparse_B = B
 
-    def step_dense(self, u, p, n):
-        """Reference-shaped step: all 2L hops over the full graph (kept for A/B comparison and for SGD / SimGCL / GMF)."""
+    def step_dense(self, u, p, n, extra_grad=None):
+        """Reference-shaped step: all 2L hops over the full graph (kept for A/B comparison and for SGD / SimGCL / GMF).  extra_grad(out): adds a
+        further loss's gradient into G after the BPR kernel (step_apr)."""
         L, A = self.L, self.A
         out = self.forward()
         lo = self.loss_and_grad_out(out, u, p, n)
+        if extra_grad is not None:
+            extra_grad(out)
         self.t += 1
         if self.optimizer == 'adam' and L > 0 and not self.skip0:
             acc, _ = self._dense_hops(self.G)

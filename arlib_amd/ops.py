@@ -1934,3 +1934,18 @@ from .profilegen import (PAIR_MLP_MAX_H, GUMBEL_MAX_K, pair_mlp_supported, gumbe
 from .policyhead import (POLICYHEAD_WIDTHS, POLICYHEAD_MAX_ROWS, bernoulli_softmax_supported, pack_bits, unpack_bits, bernoulli_softmax_eval,  # noqa: E402,F401
                          bernoulli_softmax_eval_composed, bernoulli_softmax, bernoulli_softmax_head, bernoulli_uniforms, bernoulli_softmax_sample,
                          bernoulli_softmax_sample_composed, bernoulli_softmax_sample_auto)
+
+
+# ------------------------------------------------------------------------------------------------ ops kept in modules of their own
+_ADVPAIR = ('bpr_adv_fwd_bwd', 'bpr_adv_supported', 'BPR_ADV_MAX_BATCH', 'BPR_ADV_MAX_WIDTH')
+
+
+def __getattr__(name):
+    """ops.bpr_adv_fwd_bwd / ops.bpr_adv_supported: APR's adversarial-BPR op lives in arlib_amd/advpair.py (as the pair losses live in pairloss.py,
+    each with the poisoned-memory tests of its own module) and is reachable here beside bpr_l2_fwd_bwd; bound on first use."""
+    if name in _ADVPAIR:
+        from . import advpair
+        for k in _ADVPAIR:
+            globals()[k] = getattr(advpair, k)
+        return globals()[name]
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))

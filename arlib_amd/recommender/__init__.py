@@ -1,3 +1,4 @@
-from .DirectAU import DirectAU  # noqa: F401  (the one model without a counterpart file in the reference's recommender/)
+from .DirectAU import DirectAU  # noqa: F401  (a model without a counterpart file in the reference's recommender/)
+from .APR import APR  # noqa: F401  (likewise: the defended victim)
 
-__all__ = ['DirectAU']
+__all__ = ['DirectAU', 'APR']

@@ -505,6 +505,7 @@ class Recommender:
                     if adj is not None:
                         rec_user_emb.retain_grad(); rec_item_emb.retain_grad()
                     user_emb, pos_item_emb, neg_item_emb = rec_user_emb[ul], rec_item_emb[pl], rec_item_emb[nl]
+                self._batch_index = (ul, pl, nl)
                 batch_loss = self._batch_loss(user_emb, pos_item_emb, neg_item_emb, self.args.reg * self.l2_scale)
                 if self.l2_on_negatives:
                     batch_loss = batch_loss + l2_reg_loss(self.args.reg * self.l2_scale, neg_item_emb)

@@ -1,7 +1,8 @@
 """Loss functions with the reference's names and semantics (util/loss.py: all ten), computed by the HIP
 kernels and differentiable through torch.autograd (custom Functions; backward is another kernel, not autograd of
 ATen ops).  Inputs are GPU fp32 tensors; there is no CPU fallback (wrmf_loss, alignment_loss and uniformity_loss also take other tensors, as the
-reference functions; kl_divergence and js_divergence are on no model's path and are composed from torch ops).
+reference functions; kl_divergence and js_divergence are on no model's path and are composed from torch ops).  adv_bpr_loss, APR's adversarial term,
+is an addition to the reference's ten and also takes other tensors.
 """
 import torch
 import torch.nn.functional as F
@@ -79,6 +80,69 @@ def l2_reg_loss(reg, *args):
 def bpr_l2_loss(user_emb, pos_item_emb, neg_item_emb, reg):
     """bpr_loss(u,p,n) + l2_reg_loss(reg,u,p) in one fused forward and one fused backward kernel."""
     return _BprL2Rows.apply(user_emb, pos_item_emb, neg_item_emb, float(reg), 'both')
+
+
+class _AdvBprRows(torch.autograd.Function):
+    """APR's adversarial BPR term on already-gathered [B,d] rows (fused kernel over a packed copy); the kernel computes the loss and its gradient
+    in the forward call, the backward scales it."""
+
+    @staticmethod
+    def forward(ctx, user_emb, pos_emb, neg_emb, eps, groups):
+        B = user_emb.shape[0]
+        packed = torch.cat([user_emb, pos_emb, neg_emb], 0).contiguous()
+        ar = torch.arange(B, dtype=torch.int32, device=packed.device)
+        G = torch.zeros_like(packed) if any(ctx.needs_input_grad[:3]) else None
+        out = ops.bpr_adv_fwd_bwd(packed, B, ar, ar, ar + B, eps, groups=groups, G=G, check_range=False, distinct_rows=True)
+        ctx.B = B
+        ctx.save_for_backward(G)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        (G,) = ctx.saved_tensors
+        B = ctx.B
+        G = G * gout
+        return G[:B], G[B:2 * B], G[2 * B:], None, None
+
+
+def _bpr_composed(u, p, n):
+    return torch.mean(-torch.log(10e-8 + torch.sigmoid(torch.mul(u, p).sum(dim=1) - torch.mul(u, n).sum(dim=1))))
+
+
+def _adv_delta_composed(user_emb, pos_emb, neg_emb, eps, groups):
+    """The perturbation of every row of cat(user_emb, pos_emb, neg_emb), [3B, d], detached: the clean BPR's gradient per position by autograd,
+    summed per group and normalised row-wise."""
+    B = user_emb.shape[0]
+    with torch.enable_grad():
+        rows = torch.cat([user_emb, pos_emb, neg_emb], 0).detach().requires_grad_(True)
+        (gamma,) = torch.autograd.grad(_bpr_composed(rows[:B], rows[B:2 * B], rows[2 * B:]), rows)
+    if groups is not None:
+        _, inv = torch.unique(groups.to(gamma.device), return_inverse=True)
+        gamma = torch.zeros(int(inv.max()) + 1, gamma.shape[1], dtype=gamma.dtype, device=gamma.device).index_add_(0, inv, gamma)[inv]
+    return eps * gamma * torch.rsqrt(torch.clamp((gamma * gamma).sum(dim=1, keepdim=True), min=1e-12))
+
+
+def _adv_bpr_composed(user_emb, pos_emb, neg_emb, eps, groups):
+    """adv_bpr_loss from torch ops, any device and dtype: BPR on the rows moved by _adv_delta_composed."""
+    B = user_emb.shape[0]
+    delta = _adv_delta_composed(user_emb, pos_emb, neg_emb, eps, groups)
+    return _bpr_composed(user_emb + delta[:B], pos_emb + delta[B:2 * B], neg_emb + delta[2 * B:])
+
+
+def adv_bpr_loss(user_emb, pos_emb, neg_emb, eps, groups=None):
+    """APR's adversarial term (He et al., SIGIR'18; the reference has none): bpr_loss on the rows moved by delta = eps * l2_normalize(Gamma), Gamma
+    the gradient of bpr_loss(user_emb, pos_emb, neg_emb) summed per node, delta a constant of the step.  groups: integer [3B], the node of each
+    row of cat(user_emb, pos_emb, neg_emb) (ids >= 0); None: every row is its own node (a per-sample perturbation).  GPU fp32 rows of a shape
+    ops.bpr_adv_supported covers run the fused kernel; other tensors (CPU, float64, larger batches or widths) take the same steps from torch ops."""
+    B = user_emb.shape[0]
+    if groups is not None:
+        if groups.dim() != 1 or groups.numel() != 3 * B or groups.is_floating_point():
+            raise ValueError('adv_bpr_loss: groups must be an integer tensor of length 3B = %d' % (3 * B))
+    if _kernel_rows(user_emb, pos_emb, neg_emb) and user_emb.shape == pos_emb.shape == neg_emb.shape and ops.bpr_adv_supported(B, user_emb.shape[1]):
+        if groups is not None:
+            groups = groups.to(device=user_emb.device, dtype=torch.int32).contiguous()
+        return _AdvBprRows.apply(user_emb, pos_emb, neg_emb, float(eps), groups)
+    return _adv_bpr_composed(user_emb, pos_emb, neg_emb, eps, groups)
 
 
 class _WrmfL2Rows(torch.autograd.Function):

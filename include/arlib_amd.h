@@ -379,6 +379,25 @@ int arl_wrmf_l2_fwd_bwd_f32(const float *emb, int64_t d, int64_t item_off, const
                             arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Adversarial BPR term of APR / AMF (He et al., SIGIR'18; no counterpart in the reference), forward + backward in one call
+ * (csrc/arl_advpair.hip).  Positions t = b (user of sample b), B + b (positive), 2B + b (negative); a position's row is READ at
+ * emb[u[b]] / emb[item_off + p[b]] / emb[item_off + n[b]]; its NODE is groups[t] (int32 [3B], >= 0), or with groups == NULL the
+ * row id itself, or with groups == NULL and distinct_rows the position (a per-sample perturbation).
+ *   Gamma_g = sum, in ascending t, of d bpr / d(row of position t) over the positions of node g (bpr = the mean of
+ *             arl_bpr_l2_fwd_bwd_f32's loss_out[0]);   delta_g = eps * Gamma_g / sqrt(max(|Gamma_g|^2, 1e-12))
+ *   loss_out[0] = adv = mean_b -log(10e-8 + sigmoid(<u', p'> - <u', n'>)) on rows x' = x + delta_node(x);  loss_out[1] = clean bpr
+ *   G[row] += upstream * d adv / d emb[row] with delta held constant, duplicates in ascending t on top of what G holds (no float
+ *             atomics, bit-identical from run to run); distinct_rows: the 3B read rows are pairwise distinct (plain store-add).
+ *   G may be NULL (losses only); delta_out: NULL or [3B, d], the perturbation each position received.
+ * 1 <= d <= 256 (else ARL_E_DIM) and 3B <= 16384 (else ARL_E_RANGE): Gamma must be complete before any delta exists, so the
+ * ownership scan is one window.  workspace: arl_bpr_adv_workspace_bytes(B, d) bytes (0 = unsupported shape).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t arl_bpr_adv_workspace_bytes(int64_t B, int64_t d);
+int arl_bpr_adv_fwd_bwd_f32(const float *emb, int64_t d, int64_t item_off, const int32_t *u, const int32_t *p, const int32_t *n, int64_t B,
+                            const int32_t *groups, float eps, float upstream, float *loss_out, float *G, float *delta_out, void *workspace,
+                            int32_t distinct_rows, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * White-box attack primitives.
  * ---------------------------------------------------------------------------------------------- */
 /* ------------------------------------------------------------------------------------------------
