@@ -132,6 +132,8 @@ _SIGS = {
     'arl_colsoftmax_target_loss_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'arl_bce_allpairs_workspace_bytes': (_i64, [_i64, _i64, _i64, _i32]),
     'arl_bce_allpairs_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'arl_target_rank_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'arl_target_rank_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'arl_pair_mlp_fwd_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     'arl_pair_mlp_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'arl_pair_mlp_bwd_f32': (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

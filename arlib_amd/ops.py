@@ -1935,6 +1935,11 @@ from .policyhead import (POLICYHEAD_WIDTHS, POLICYHEAD_MAX_ROWS, bernoulli_softm
                          bernoulli_softmax_eval_composed, bernoulli_softmax, bernoulli_softmax_head, bernoulli_uniforms, bernoulli_softmax_sample,
                          bernoulli_softmax_sample_composed, bernoulli_softmax_sample_auto)
 
+# ================================================================================================ full-ranking attack metrics (csrc/arl_targetrank.hip)
+# (module of its own: arlib_amd/targetrank.py, with its poisoned-memory runs in tests/test_gpu_targetrank_poison.py)
+from .targetrank import (TARGETRANK_WIDTHS, TARGETRANK_MAX_TARGETS, TARGETRANK_MAX_ROWS, target_rank_supported, target_rank_kernel,  # noqa: E402,F401
+                         target_rank_composed, target_rank)
+
 
 # ------------------------------------------------------------------------------------------------ ops kept in modules of their own
 _ADVPAIR = ('bpr_adv_fwd_bwd', 'bpr_adv_supported', 'BPR_ADV_MAX_BATCH', 'BPR_ADV_MAX_WIDTH')

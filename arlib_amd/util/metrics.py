@@ -154,3 +154,91 @@ class AttackMetric(object):
             idcg = disc[:min(k, len(self.targetItem))].sum()
             out.append(float((h[:, :k] * disc).sum() / (idcg * h.shape[0])))
         return out
+
+
+class TargetRankMetric(object):
+    """Full-ranking attack metrics: the rank of every target item for every user over the whole catalogue (ops.target_rank, one call), and everything
+    that follows from it.  targetItem: internal item ids (distinct).  top: any k up to the number of items.  mask_train=True leaves each user's training
+    interactions out of the ranking; a pair whose target the user already has gets rank -1 and drops out of every count below, while the user-level
+    denominators of the four reference formulas stay as they are.
+
+    hitRate / precision / recall / NDCG are AttackMetric's formulas (reference util/metrics.py:125-208) with hit[u, r] read as "some target of user u has
+    rank r": they depend on `rank < k` and `disc[rank]` only, so the rank matrix serves them at every k without a top-k list."""
+
+    def __init__(self, recommendModel, targetItem, top=[10], mask_train=False):
+        self.recommendModel = recommendModel
+        self.targetItem = targetItem
+        self.top = top
+        self.mask_train = mask_train
+        self._rank = None
+
+    def ranks(self):
+        """int32 [U, T]: 0-based rank of target t in user u's descending score row (ties by item id), -1 where the pair is masked."""
+        if self._rank is None:
+            import torch
+            from .. import ops
+            rm = self.recommendModel
+            dev = rm.user_emb.device
+            ids = [rm.data.user[u] for u in rm.data.user]
+            uid = torch.tensor(ids, dtype=torch.long, device=dev)
+            Pu, Pi = rm.user_emb[uid].detach().float().contiguous(), rm.item_emb.detach().float().contiguous()
+            targets = torch.tensor([int(t) for t in self.targetItem], dtype=torch.int32, device=dev)
+            mask = None
+            if self.mask_train:
+                m = rm.data.matrix().tocsr()[np.asarray(ids, np.int64)]
+                m.sum_duplicates()
+                m.sort_indices()
+                mask = (torch.from_numpy(m.indptr.astype(np.int32)).to(dev), torch.from_numpy(m.indices.astype(np.int32)).to(dev))
+            rank, _ = ops.target_rank(Pu, Pi, targets, mask)
+            self._rank = rank.cpu().numpy()
+        return self._rank
+
+    def _below(self, k):
+        r = self.ranks()
+        return (r >= 0) & (r < k)
+
+    def precision(self):
+        r = self.ranks()
+        return [float(self._below(k).sum() / (r.shape[0] * k)) for k in self.top]
+
+    def hitRate(self):
+        r = self.ranks()
+        return [float((self._below(k).any(1) / r.shape[1]).sum() / r.shape[0]) for k in self.top]
+
+    def recall(self):
+        r = self.ranks()
+        return [float(self._below(k).sum() / (r.shape[0] * r.shape[1])) for k in self.top]
+
+    def NDCG(self):
+        r = self.ranks()
+        out = []
+        for k in self.top:
+            disc = 1.0 / np.log2(2 + np.arange(k))
+            idcg = disc[:min(k, r.shape[1])].sum()
+            b = self._below(k)
+            out.append(float(disc[r[b]].sum() / (idcg * r.shape[0])))
+        return out
+
+    def meanRank(self):
+        """Mean over the valid pairs of the 1-based rank."""
+        r = self.ranks()
+        v = r >= 0
+        return float((r[v].astype(np.float64) + 1.0).mean()) if v.any() else float('nan')
+
+    def MRR(self):
+        """Mean over the valid pairs of 1 / (1-based rank)."""
+        r = self.ranks()
+        v = r >= 0
+        return float((1.0 / (r[v].astype(np.float64) + 1.0)).mean()) if v.any() else float('nan')
+
+    def exposure(self, per_target=False):
+        """ER@K for each K of `top`: per target, the share of its valid pairs with rank < K; averaged over the targets that have a valid pair
+        (per_target=True: the [T] array itself, NaN for a target without one)."""
+        r = self.ranks()
+        valid = (r >= 0).sum(0).astype(np.float64)
+        out = []
+        for k in self.top:
+            with np.errstate(invalid='ignore', divide='ignore'):
+                share = self._below(k).sum(0) / valid
+            out.append(share if per_target else (float(np.nanmean(share)) if (valid > 0).any() else float('nan')))
+        return out

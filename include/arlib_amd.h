@@ -654,6 +654,24 @@ int arl_bce_allpairs_f32(const float *Pu, int64_t R, const float *Pi, int64_t I,
                          arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Full-ranking attack metrics: the rank of each target item for each user (csrc/arl_targetrank.hip; the sufficient statistic of the
+ * reference's AttackMetric, util/metrics.py:125-208).  Pu [U, d], Pi [I, d] fp32, 16-byte aligned; targets [T] int32, distinct, in [0, I).
+ * With s = Pu Pi^T in exact fp32 (one instruction sequence for every score that is compared):
+ *   rank [U, T] int32 : #{ j != targets[t], (u, j) not masked : s[u, j] > s[u, targets[t]] or (equal and j < targets[t]) }, the 0-based
+ *                       position of the target in user u's descending row with ties broken by item id; -1 where (u, targets[t]) is masked
+ *   tscore [U, T] fp32: s[u, targets[t]], the thresholds the counts were taken against
+ *   mask_rowptr [U + 1], mask_col [nnz] | both NULL: pairs left out of the count, CSR by user, int32, each row sorted and distinct.
+ * Limits: d in {16, 32, 64, 128}, 1 <= T <= 64, 1 <= U, I <= (2^31 - 1) / 128; anything else is ARL_E_RANGE.  Integer counts, no atomics:
+ * bit-identical from run to run.  The workspace (arl_target_rank_workspace_bytes; 0 when the item stream is not split or the shape is
+ * outside the limits) needs no initialisation. */
+/* util/metrics.py:125-208 */
+int64_t arl_target_rank_workspace_bytes(int64_t U, int64_t I, int64_t d, int64_t T);
+/* util/metrics.py:125-208 */
+int arl_target_rank_f32(const float *Pu, int64_t U, const float *Pi, int64_t I, int64_t d, const int32_t *targets, int64_t T,
+                        const int32_t *mask_rowptr, const int32_t *mask_col, int32_t *rank, float *tscore, void *workspace,
+                        arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * GSPAttack's profile generator (csrc/arl_profilegen.hip; reference attack/Black/GSPAttack.py:120-130, 201-202, 224-231 as repaired in
  * arlib_amd/attack/Black/GSPAttack.py).  Every pointer 16-byte aligned; ARL_E_DIM for H > 1024 or k > 512, ARL_E_RANGE for F or I outside
  * the kernels' grids (F <= 524 280 for the pair MLP, I <= 2^31 - 2049, F * ceil(I / 256) [* k for the noise] < 2^31), ARL_E_ARG for an
