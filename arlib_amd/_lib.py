@@ -145,6 +145,8 @@ _SIGS = {
     'arl_bernoulli_softmax_eval_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'arl_bernoulli_softmax_sample_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, C.c_uint64, C.c_uint64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     'arl_bernoulli_uniforms_f32': (C.c_int, [C.c_uint64, C.c_uint64, _i64, _i64, _i64, _vp, _vp]),
+    'arl_multinomial_softmax_workspace_bytes': (_i64, [_i64, _i64, _i64, _i32]),
+    'arl_multinomial_softmax_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'arl_kmeans_assign_f32':(C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     'arl_kmeans_chunk_rows': (_i64, []),
     'arl_kmeans_update_workspace_bytes': (_i64, [_i64, _i64, _i64]),

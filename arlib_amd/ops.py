@@ -1954,3 +1954,8 @@ def __getattr__(name):
             globals()[k] = getattr(advpair, k)
         return globals()[name]
     raise AttributeError('module %r has no attribute %r' % (__name__, name))
+
+# ================================================================================================ the autoencoders' multinomial likelihood (csrc/arl_multinomial.hip)
+# (module of its own: arlib_amd/multinomial.py, with its poisoned-memory runs in tests/test_gpu_multinomial_poison.py)
+from .multinomial import (MULTINOMIAL_WIDTHS, MULTINOMIAL_MAX_ROWS, multinomial_softmax_supported, multinomial_softmax_kernel,  # noqa: E402,F401
+                          multinomial_softmax_composed, multinomial_softmax, multinomial_nll)

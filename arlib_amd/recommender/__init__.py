@@ -1,4 +1,5 @@
 from .DirectAU import DirectAU  # noqa: F401  (a model without a counterpart file in the reference's recommender/)
 from .APR import APR  # noqa: F401  (likewise: the defended victim)
+from .MultVAE import MultVAE  # noqa: F401  (likewise: the inductive victim)
 
-__all__ = ['DirectAU', 'APR']
+__all__ = ['DirectAU', 'APR', 'MultVAE']

@@ -2,12 +2,14 @@
 kernels and differentiable through torch.autograd (custom Functions; backward is another kernel, not autograd of
 ATen ops).  Inputs are GPU fp32 tensors; there is no CPU fallback (wrmf_loss, alignment_loss and uniformity_loss also take other tensors, as the
 reference functions; kl_divergence and js_divergence are on no model's path and are composed from torch ops).  adv_bpr_loss, APR's adversarial term,
-is an addition to the reference's ten and also takes other tensors.
+is an addition to the reference's ten and also takes other tensors; so is multinomial_nll, the autoencoders' likelihood
+(arlib_amd/multinomial.py), whose composed route runs on the CPU too.
 """
 import torch
 import torch.nn.functional as F
 
 from .. import ops, pairloss
+from ..multinomial import multinomial_nll  # noqa: F401
 
 
 def _i32(t):

@@ -734,6 +734,28 @@ int arl_bernoulli_softmax_sample_f32(const float *q, int64_t B, const float *E, 
 int arl_bernoulli_uniforms_f32(uint64_t seed, uint64_t call, int64_t row0, int64_t B, int64_t I, float *out, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The multinomial likelihood of the autoencoder recommenders (csrc/arl_multinomial.hip; Mult-DAE / Mult-VAE, Liang et al., WWW'18; no counterpart
+ * in the reference) -- a softmax over every item for each batch row, read at the row's positives, with no B x I tensor.  q [B, d] the rows'
+ * last activations, E [I, d] the output-layer weight, fp32; the positives as CSR (rowptr [B + 1], col [nnz] int32, sorted and distinct within a
+ * row, val [nnz] fp32 weights w | NULL: every w is 1), g [B] the per-row upstream.  With z = q E^T, lse_b = log sum_i exp z_bi,
+ * n_b = sum_{i in pos(b)} w_bi and p = softmax_i(z):
+ *   nll[b] = n_b lse_b - sum_{i in pos(b)} w_bi z_bi
+ *   dq[b]  = g_b ( n_b sum_i p_bi E_i - sum_{i in pos(b)} w_bi E_i )
+ *   dE[i]  = sum_b g_b ( n_b p_bi - w_bi [i in pos(b)] ) q_b
+ * A row without positives gives nll = 0 and contributes nothing to either gradient.  nll [B] and lse [B] are always written; dq [B, d] and
+ * dE [I, d] are each written when not NULL and then need g.  dE also needs the positives by item: trowptr [I + 1], tcol [nnz] the row ids, and with
+ * val tperm [nnz], the entries' positions in the by-row arrays.  The index arrays are trusted.
+ * d in {16, 32, 64, 128} (else ARL_E_DIM), B, I >= 1 and nnz >= 0 (else ARL_E_ARG), B, I <= (2^31 - 1) / 128 and nnz < 2^31 (else ARL_E_RANGE),
+ * q, E, dq, dE and the workspace 16-byte aligned (else ARL_E_ARG); a missing pointer is ARL_E_NULL; all checked before any launch.  Exact fp32
+ * products on v_mfma_f32_16x16x4_f32, an online maximum for the log-sum-exp, no atomics and fixed-order sums: bit-identical from run to run.
+ * The workspace (arl_multinomial_softmax_workspace_bytes, want_grad = 1 when dq or dE is asked for; 0 for a shape outside the limits) needs
+ * no initialisation. */
+int64_t arl_multinomial_softmax_workspace_bytes(int64_t B, int64_t I, int64_t d, int32_t want_grad);
+int arl_multinomial_softmax_f32(const float *q, int64_t B, const float *E, int64_t I, int64_t d, const int32_t *rowptr, const int32_t *col, const float *val, int64_t nnz,
+                                const int32_t *trowptr, const int32_t *tcol, const int32_t *tperm, const float *g, float *nll, float *lse, float *dq, float *dE,
+                                void *workspace, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Lloyd's k-means for NCL's prototypes (csrc/arl_kmeans.hip).  Replaces recommender/NCL.py:52-73 (e_step / run_kmeans: sklearn's KMeans on
  * host copies of the tables; the commented faiss.Kmeans(gpu=True) of :61-66 is what the authors meant).  X [N, d] points, C [k, d]
  * centroids, d in {16, 32, 64, 128} (else ARL_E_DIM), N, k >= 1 (else ARL_E_ARG) and <= 2^31 / 128 (else ARL_E_RANGE), X, C and
