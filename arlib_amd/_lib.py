@@ -147,6 +147,13 @@ _SIGS = {
     'arl_bernoulli_uniforms_f32': (C.c_int, [C.c_uint64, C.c_uint64, _i64, _i64, _i64, _vp, _vp]),
     'arl_multinomial_softmax_workspace_bytes': (_i64, [_i64, _i64, _i64, _i32]),
     'arl_multinomial_softmax_f32': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'arl_als_default_split_len': (_i64, []),
+    'arl_als_gram_workspace_bytes': (_i64, [_i64, _i64]),
+    'arl_als_gram_f64': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    'arl_als_solve_rows_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'arl_als_solve_rows_f32': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, C.c_double, C.c_double, _i64, _vp, _vp, _vp]),
+    'arl_als_objective_workspace_bytes': (_i64, [_i64, _i64, _i64]),
+    'arl_als_objective_f64': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     'arl_kmeans_assign_f32':(C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     'arl_kmeans_chunk_rows': (_i64, []),
     'arl_kmeans_update_workspace_bytes': (_i64, [_i64, _i64, _i64]),

@@ -1959,3 +1959,8 @@ def __getattr__(name):
 # (module of its own: arlib_amd/multinomial.py, with its poisoned-memory runs in tests/test_gpu_multinomial_poison.py)
 from .multinomial import (MULTINOMIAL_WIDTHS, MULTINOMIAL_MAX_ROWS, multinomial_softmax_supported, multinomial_softmax_kernel,  # noqa: E402,F401
                           multinomial_softmax_composed, multinomial_softmax, multinomial_nll)
+
+# ================================================================================================ alternating least squares (csrc/arl_als.hip)
+# (module of its own: arlib_amd/als.py, with its poisoned-memory runs in tests/test_gpu_als_poison.py)
+from .als import (ALS_WIDTHS, ALS_MAX_ROWS, als_supported, gram, als_solve_rows_kernel, als_solve_rows_composed, als_solve_rows,  # noqa: E402,F401
+                  als_objective)

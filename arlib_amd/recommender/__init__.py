@@ -1,5 +1,6 @@
 from .DirectAU import DirectAU  # noqa: F401  (a model without a counterpart file in the reference's recommender/)
 from .APR import APR  # noqa: F401  (likewise: the defended victim)
 from .MultVAE import MultVAE  # noqa: F401  (likewise: the inductive victim)
+from .iALS import iALS  # noqa: F401  (likewise: the ALS-trained WRMF victim)
 
-__all__ = ['DirectAU', 'APR', 'MultVAE']
+__all__ = ['DirectAU', 'APR', 'MultVAE', 'iALS']

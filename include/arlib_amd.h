@@ -756,6 +756,37 @@ int arl_multinomial_softmax_f32(const float *q, int64_t B, const float *E, int64
                                 void *workspace, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Alternating least squares for implicit feedback (csrc/arl_als.hip; WRMF as published, Hu, Koren, Volinsky, ICDM'08; the reference's WRMF is
+ * a sampled SGD approximation and is untouched).  Y [n, d] the OTHER table, fp32; the rows to solve as CSR (rowptr [n_rows + 1], col [nnz] int32
+ * in [0, n), val [nnz] fp32 weights w | NULL: every w is 1).  With p = 1 on the stored entries and confidence c = 1 + alpha w:
+ *   L   = sum_u sum_i c_ui (p_ui - x_u . y_i)^2 + lambda (|X|^2 + |Y|^2)          over ALL (u, i)
+ *   G   = Y^T Y                                                                   (arl_als_gram_f64: d x d, double)
+ *   A_r = G + alpha sum_{i in P_r} w_ri y_i y_i^T + lambda I,   b_r = sum_{i in P_r} (1 + alpha w_ri) y_i,   x_r = A_r^-1 b_r     (arl_als_solve_rows_f32)
+ *   L   = sum_u [ x_u^T G x_u + sum_{i in P_u} ((1 + alpha w)(1 - s)^2 - s^2) ] + lambda (|X|^2 + |Y|^2),   s = x_u . y_i         (arl_als_objective_f64)
+ * gram      : G [d, d] double, summed over at most 256 fixed spans of rows in ascending order (products of fp32 values are exact in double).
+ * solve_rows: X [n_solve, d]: row j is the solution of CSR row rows[j] (rows [n_solve] int32 in [0, n_rows), repeats allowed) or of row j when
+ *             rows is NULL (then n_solve = n_rows).  nnz_listed = the listed rows' entries in total (nnz without rows; it sizes the workspace).
+ *             The rank-n_r update runs exact fp32 on v_mfma_f32_16x16x4_f32 over the lower-triangular tiles (a stage of 64 entries in fp32, the
+ *             stages in double), A_r is completed, factorised and solved in double.  A row longer than split_len (<= 0: the default,
+ *             arl_als_default_split_len) is cut into pieces of split_len entries, accumulated by separate workgroups and added in piece order;
+ *             a row without entries gives exactly 0.  alpha, lambda >= 0 (lambda > 0 keeps A_r positive definite whatever the row).
+ * objective : out [1] double; X [n_rows, d] the rows' table, G the Gram matrix of Y; no n_rows x n score matrix.
+ * d in {16, 32, 64, 128} (else ARL_E_DIM), sizes >= 1 (else ARL_E_ARG), n, n_rows, n_solve <= (2^31 - 1) / 128 and nnz_listed < 2^31 (else
+ * ARL_E_RANGE), tables, G and workspaces 16-byte aligned (else ARL_E_ARG); a missing pointer is ARL_E_NULL; all checked before any launch.  The
+ * index arrays are trusted.  No atomics, fixed-order sums: bit-identical from run to run (for a given split_len).  The workspaces
+ * (*_workspace_bytes; 0 for a shape outside the limits) need no initialisation. */
+int64_t arl_als_default_split_len(void);
+int64_t arl_als_gram_workspace_bytes(int64_t n, int64_t d);
+int arl_als_gram_f64(const float *Y, int64_t n, int64_t d, double *G, void *workspace, arl_stream_t stream);
+int64_t arl_als_solve_rows_workspace_bytes(int64_t n_solve, int64_t nnz_listed, int64_t d, int64_t split_len);
+int arl_als_solve_rows_f32(const float *Y, int64_t n, int64_t d, const double *G, const int32_t *rowptr, const int32_t *col, const float *val, int64_t n_rows,
+                           const int32_t *rows, int64_t n_solve, int64_t nnz_listed, double alpha, double lambda, int64_t split_len, float *X, void *workspace,
+                           arl_stream_t stream);
+int64_t arl_als_objective_workspace_bytes(int64_t n_rows, int64_t n, int64_t d);
+int arl_als_objective_f64(const float *X, int64_t n_rows, const float *Y, int64_t n, int64_t d, const double *G, const int32_t *rowptr, const int32_t *col,
+                          const float *val, double alpha, double lambda, double *out, void *workspace, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Lloyd's k-means for NCL's prototypes (csrc/arl_kmeans.hip).  Replaces recommender/NCL.py:52-73 (e_step / run_kmeans: sklearn's KMeans on
  * host copies of the tables; the commented faiss.Kmeans(gpu=True) of :61-66 is what the authors meant).  X [N, d] points, C [k, d]
  * centroids, d in {16, 32, 64, 128} (else ARL_E_DIM), N, k >= 1 (else ARL_E_ARG) and <= 2^31 / 128 (else ARL_E_RANGE), X, C and
