@@ -19,16 +19,11 @@
 #include <stdint.h>
 #include <math.h>
 #include "arlib_amd.h"
+#include "arl_util.h"
 #include "arl_ordered.h"
 
 // a + (-a) must cancel exactly (a sample with p == n leaves its item's Gamma at 0): no product is fused into the sum that follows it
 #pragma clang fp contract(off)
-
-#define ADV_LAUNCH_CHECK()                                  \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
 
 namespace {
 
@@ -221,13 +216,13 @@ int arl_bpr_adv_fwd_bwd_f32(const float *emb, int64_t d, int64_t item_off, const
     const unsigned gs = (unsigned)((B + kWaves - 1) / kWaves), gp = (unsigned)((3 * B + kWaves - 1) / kWaves);
     const size_t list = (size_t)(3 * B) * sizeof(int32_t), red = (size_t)2 * kBlk * sizeof(double);
     hipLaunchKernelGGL(adv_clean_kernel, dim3(gs), dim3(kBlk), 0, st, a, w);
-    ADV_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(adv_delta_kernel, dim3(gp), dim3(kBlk), (groups || !distinct_rows) ? list : 0, st, a, w, eps);
-    ADV_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(adv_pert_kernel, dim3(gs), dim3(kBlk), 0, st, a, w, delta_out);
-    ADV_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(adv_bwd_kernel, dim3((G ? gp : 0u) + 1u), dim3(kBlk), (!distinct_rows && list > red) ? list : red, st, a, w, upstream, G, loss_out);
-    ADV_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 

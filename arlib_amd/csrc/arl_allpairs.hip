@@ -7,9 +7,9 @@
 //     dPu[r] = upstream rw[r] sum_i g[r, i] Pi[i],     dPi[i] = upstream sum_r rw[r] g[r, i] Pu[r].
 // So the loss is a dense stream over all R x I scores (f0 only) plus a correction over the listed positives.
 //
-// Rules kept throughout, those of arl_colsoftmax.hip:
-//   * scores and the weighted row sums of the dense stream run exact fp32 on v_mfma_f32_16x16x4_f32: a wave keeps 16 rows of the RESIDENT table
-//     in registers, the STREAMED table passes through LDS 64 rows at a time (double-buffered, the streamed rows' row_weight beside it);
+// Rules kept throughout:
+//   * scores and the weighted row sums of the dense stream run exact fp32 on v_mfma_f32_16x16x4_f32 on the shared streamed tile (arl_stream.h),
+//     the streamed rows' row_weight beside each stage;
 //   * pass 1: users resident, all items streamed: rowloss and the raw dPu, one writer per row;   pass 2: items resident, users streamed in splits:
 //     raw dPi partials;   pass 3: two gather kernels over the positives, a wave per row (by user: finishes rowloss and dPu; by item: folds the splits
 //     in ascending order and finishes dPi), lane groups in a fixed order;
@@ -19,17 +19,12 @@
 #include <stdint.h>
 #include <math.h>
 #include "arlib_amd.h"
-
-#define BAP_LAUNCH_CHECK()                                  \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
+#include "arl_stream.h"
 
 namespace {
 
 constexpr int kBlk = 256, kWaves = 4;
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+using strm::f32x4v;
 
 // p = sigmoid(s) and q = sigmoid(-s) from one exp of -|s|: neither is rounded from 1 - the other.  Contraction is off so that every kernel that
 // calls these gets the same bits (the loss-only and the gradient instantiations, the by-user and the by-item gathers).
@@ -70,23 +65,15 @@ enum { BAP_ROWS_LOSS = 0, BAP_ROWS_GRAD = 1, BAP_COLS_GRAD = 2 };
 template <int D, int MODE>
 __global__ __launch_bounds__(kBlk) void bap_stream_kernel(const float *__restrict__ Xr, int nR, const float *__restrict__ Xt, int nT, int split_len,
                                                            const float *__restrict__ wt, float eps, float *__restrict__ out, float *__restrict__ rowloss) {
-    constexpr int Q = D / 4, LD = D + 4, NT = D / 16;
+    constexpr int NT = D / 16;
     constexpr bool GRAD = MODE != BAP_ROWS_LOSS, LOSS = MODE != BAP_COLS_GRAD, TW = MODE == BAP_COLS_GRAD;
-    __shared__ float tile[2][64 * LD];
+    __shared__ float tile[2][strm::kStageFloats<D>];
     __shared__ float tw[2][64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, g = lane >> 4;
     const int r0 = (blockIdx.x * kWaves + wv) * 16;
     const int t_begin = blockIdx.y * split_len, t_end = min(nT, t_begin + split_len);
-    float br[Q];
-    {
-        const int r = r0 + c;
-#pragma unroll
-        for (int i = 0; i < Q; i += 4) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < nR) v = *reinterpret_cast<const float4 *>(Xr + (size_t)r * D + Q * g + i);
-            br[i] = v.x; br[i + 1] = v.y; br[i + 2] = v.z; br[i + 3] = v.w;
-        }
-    }
+    float br[D / 4];
+    strm::load_resident<D>(Xr, r0 + c, nR, g, br);
     f32x4v o[NT];
 #pragma unroll
     for (int n = 0; n < NT; ++n) o[n] = f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -99,25 +86,18 @@ __global__ __launch_bounds__(kBlk) void bap_stream_kernel(const float *__restric
         for (int reg = 0; reg < 4; ++reg) o2[n][reg] = 0.0;
     double rl = 0.0;
     const int nst = (t_end - t_begin + 63) / 64;
-    // a stage is 64 x D floats = 16 D float4s over 256 threads; the NEXT stage is fetched into registers before the current one is consumed
-    // and goes to the other LDS buffer afterwards (macros, not lambdas: an array captured by reference stays in scratch memory)
-    constexpr int PF = 64 * (D / 4) / kBlk;
-    f32x4v pre[PF];
+    // beside a stage's rows: the streamed rows' row_weight (BAP_COLS_GRAD), fetched and stashed with them
+    strm::stage<D> stg(tid);
     float pre_w = 0.f;
-    const int frow = tid / (D / 4), fq = (tid % (D / 4)) * 4;
-    constexpr int FSTEP = kBlk / (D / 4);
-#define BAP_FETCH(ST)                                                                                                              \
-    do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) {                                                                           \
-            const int t = min(t_begin + (ST) * 64 + frow + i * FSTEP, nT - 1);     /* clamped; rows past t_end are masked below */ \
-            pre[i] = *reinterpret_cast<const f32x4v *>(Xt + (size_t)t * D + fq);                                                   \
-        }                                                                                                                          \
-        if (TW && tid < 64) pre_w = wt[min(t_begin + (ST) * 64 + tid, nT - 1)];                                                    \
+#define BAP_FETCH(ST)                                                           \
+    do {                                                                        \
+        stg.fetch(Xt, t_begin + (ST) * 64, nT);                                 \
+        if (TW && tid < 64) pre_w = wt[min(t_begin + (ST) * 64 + tid, nT - 1)]; \
     } while (0)
-#define BAP_STASH(BUF)                                                                                                             \
-    do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) *reinterpret_cast<f32x4v *>(&tile[BUF][(frow + i * FSTEP) * LD + fq]) = pre[i]; \
-        if (TW && tid < 64) tw[BUF][tid] = pre_w;                                                                                  \
+#define BAP_STASH(BUF)                            \
+    do {                                          \
+        stg.stash(tile[BUF]);                     \
+        if (TW && tid < 64) tw[BUF][tid] = pre_w; \
     } while (0)
     if (nst > 0) { BAP_FETCH(0); BAP_STASH(0); }
     __syncthreads();
@@ -128,16 +108,7 @@ __global__ __launch_bounds__(kBlk) void bap_stream_kernel(const float *__restric
         float stage_loss = 0.f;
 #pragma unroll
         for (int sub = 0; sub < 4; ++sub) {
-            f32x4v sc = f32x4v{0.f, 0.f, 0.f, 0.f};
-            const float *arow = T + (sub * 16 + c) * LD + Q * g;
-#pragma unroll
-            for (int i = 0; i < Q; i += 4) {
-                const float4 a = *reinterpret_cast<const float4 *>(arow + i);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, br[i], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, br[i + 1], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, br[i + 2], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, br[i + 3], sc, 0, 0, 0);
-            }
+            const f32x4v sc = strm::scores<D>(strm::a_row<D>(T, sub, c, g), br);
             const int tb = t_begin + st * 64 + sub * 16 + 4 * g;        // streamed row of register 0
             float fj[4], pj[4];
 #pragma unroll
@@ -150,24 +121,10 @@ __global__ __launch_bounds__(kBlk) void bap_stream_kernel(const float *__restric
                 pj[j] = live ? w0 : 0.f;
             }
             if (LOSS) stage_loss += (fj[0] + fj[1]) + (fj[2] + fj[3]);
-            if (GRAD) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float *brow = T + (sub * 16 + 4 * g + j) * LD + c;
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(pj[j], brow[16 * n], o[n], 0, 0, 0);
-                }
-            }
+            if (GRAD) strm::accumulate<D>(T, sub, c, g, pj, o);
         }
         if (LOSS) rl += (double)stage_loss;                              // 16 scores in fp32, the stages in double
-        if (GRAD) {
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) o2[n][reg] += (double)o[n][reg];
-                o[n] = f32x4v{0.f, 0.f, 0.f, 0.f};
-            }
-        }
+        if constexpr (GRAD) strm::flush_stage<D>(o, o2);
         if (st + 1 < nst) BAP_STASH(buf ^ 1);
         __syncthreads();
     }
@@ -179,16 +136,7 @@ __global__ __launch_bounds__(kBlk) void bap_stream_kernel(const float *__restric
         for (int off = 16; off <= 32; off <<= 1) rl += __shfl_xor(rl, off);
         if (g == 0 && r0 + c < nR) rowloss[r0 + c] = (float)rl;
     }
-    if (GRAD) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int r = r0 + 4 * g + reg;
-                if (r >= nR) continue;
-                out[((size_t)blockIdx.y * nR + r) * D + 16 * n + c] = (float)o2[n][reg];
-            }
-    }
+    if constexpr (GRAD) strm::store_partial<D>(out, blockIdx.y, nR, r0, g, c, o2);
 }
 
 // Pass 3, a wave per row x of the resident table X [n, D]; its listed entries k in [ptr[x], ptr[x + 1]) name rows col[k] of the other table Y and
@@ -262,19 +210,6 @@ __global__ __launch_bounds__(kBlk) void bap_loss_kernel(const float *__restrict_
     if (threadIdx.x == 0) loss[0] = (float)red[0];
 }
 
-// splits of the streamed users when the items are resident: arl_colsoftmax.hip's rule (enough workgroups to fill the chip several times over, at
-// least 4 096 streamed rows each)
-int bap_splits(int64_t nR, int64_t nT) {
-    const int64_t row_blocks = (nR + 63) / 64;
-    int64_t s = (2048 + row_blocks - 1) / row_blocks;
-    const int64_t max_s = (nT + 4095) / 4096;
-    if (s > max_s) s = max_s;
-    if (s > 256) s = 256;
-    return (int)(s < 1 ? 1 : s);
-}
-
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 template <int D>
 int bap_run(const float *Pu, int64_t R, const float *Pi, int64_t I, const int32_t *rowptr, const int32_t *col, const float *val, const int32_t *trowptr,
             const int32_t *tcol, const int32_t *tperm, const float *rw, float eps, float upstream, float *rowloss, float *loss, float *dPu, float *dPi,
@@ -283,36 +218,32 @@ int bap_run(const float *Pu, int64_t R, const float *Pi, int64_t I, const int32_
     const dim3 grid_users((unsigned)((R + 63) / 64), 1u), wave_users((unsigned)((R + kWaves - 1) / kWaves)), wave_items((unsigned)((I + kWaves - 1) / kWaves));
     if (dPu) {
         hipLaunchKernelGGL((bap_stream_kernel<D, BAP_ROWS_GRAD>), grid_users, blk, 0, st, Pu, (int)R, Pi, (int)I, (int)I, (const float *)nullptr, eps, dPu, rowloss);
-        BAP_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
         hipLaunchKernelGGL((bap_gather_kernel<D, true>), wave_users, blk, 0, st, Pu, (int)R, Pi, rowptr, col, val, (const int32_t *)nullptr, rw, (const float *)nullptr, eps,
                            upstream, (const float *)dPu, 1, dPu, rowloss);
-        BAP_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
     } else {
         hipLaunchKernelGGL((bap_stream_kernel<D, BAP_ROWS_LOSS>), grid_users, blk, 0, st, Pu, (int)R, Pi, (int)I, (int)I, (const float *)nullptr, eps, (float *)nullptr,
                            rowloss);
-        BAP_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
         hipLaunchKernelGGL((bap_gather_kernel<D, false>), wave_users, blk, 0, st, Pu, (int)R, Pi, rowptr, col, val, (const int32_t *)nullptr, rw, (const float *)nullptr, eps,
                            upstream, (const float *)nullptr, 0, (float *)nullptr, rowloss);
-        BAP_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(bap_loss_kernel, dim3(1), blk, 0, st, rw, (const float *)rowloss, (int)R, loss);
-    BAP_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     if (dPi) {
-        const int ns = bap_splits(I, R);
+        const int ns = strm::split_count(I, R);
         const int split_len = (int)((R + ns - 1) / ns);
         float *gpart = (float *)ws;
         hipLaunchKernelGGL((bap_stream_kernel<D, BAP_COLS_GRAD>), dim3((unsigned)((I + 63) / 64), (unsigned)ns), blk, 0, st, Pi, (int)I, Pu, (int)R, split_len, rw, eps, gpart,
                            (float *)nullptr);
-        BAP_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
         hipLaunchKernelGGL((bap_gather_kernel<D, true>), wave_items, blk, 0, st, Pi, (int)I, Pu, trowptr, tcol, val, tperm, (const float *)nullptr, rw, eps, upstream,
                            (const float *)gpart, ns, dPi, (float *)nullptr);
-        BAP_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
     }
     return ARL_OK;
-}
-
-bool bap_shape_ok(int64_t R, int64_t I, int64_t d) {
-    return (d == 16 || d == 32 || d == 64 || d == 128) && R > 0 && I > 0 && R <= 0x7fffffffll / 128 && I <= 0x7fffffffll / 128;
 }
 
 }  // namespace
@@ -320,8 +251,8 @@ bool bap_shape_ok(int64_t R, int64_t I, int64_t d) {
 extern "C" {
 
 int64_t arl_bce_allpairs_workspace_bytes(int64_t R, int64_t I, int64_t d, int32_t want_grad) {
-    if (!bap_shape_ok(R, I, d)) return 0;
-    return want_grad ? (int64_t)up16(sizeof(float) * (size_t)bap_splits(I, R) * (size_t)I * (size_t)d) : 0;
+    if (!strm::shape_ok(R, I, d)) return 0;
+    return want_grad ? (int64_t)up16(sizeof(float) * (size_t)strm::split_count(I, R) * (size_t)I * (size_t)d) : 0;
 }
 
 int arl_bce_allpairs_f32(const float *Pu, int64_t R, const float *Pi, int64_t I, int64_t d, const int32_t *pos_rowptr, const int32_t *pos_col, const float *pos_val,
@@ -336,10 +267,7 @@ int arl_bce_allpairs_f32(const float *Pu, int64_t R, const float *Pi, int64_t I,
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
 #define BAP_RUN(DD) return bap_run<DD>(Pu, R, Pi, I, pos_rowptr, pos_col, pos_val, post_rowptr, post_col, post_perm, row_weight, eps, upstream, rowloss, loss, dPu, dPi, ws, st)
-    if (d == 16) BAP_RUN(16);
-    if (d == 32) BAP_RUN(32);
-    if (d == 64) BAP_RUN(64);
-    BAP_RUN(128);
+    ARL_DISPATCH_WIDTH(d, BAP_RUN);
 #undef BAP_RUN
 }
 

@@ -22,12 +22,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "arlib_amd.h"
-
-#define ALS_LAUNCH_CHECK()                                  \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
+#include "arl_util.h"
 
 namespace {
 
@@ -37,8 +32,6 @@ constexpr int kGramSpans = 256, kGramSpanRows = 128, kGramStage = 32;
 constexpr int kPlanBlk = 1024;
 constexpr int kSumParts = 256;
 typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 // ------------------------------------------------------------------------------------------------ Gram
 // part [span][D * D] = sum over the span's rows, ascending, of y y^T in double (an fp32 product is exact in double).  Thread (ty, tx) owns the
@@ -489,15 +482,15 @@ int als_solve_run(const float *Y, const double *G, const int32_t *rowptr, const 
     int32_t *piece_off = (int32_t *)ws;
     unsigned char *parts = (unsigned char *)(ws + up16(sizeof(int32_t) * (size_t)(n_solve + 1)));
     hipLaunchKernelGGL(als_plan_kernel, dim3(1), dim3(kPlanBlk), 0, st, rowptr, rows, (int)n_solve, (int)split_len, piece_off);
-    ALS_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     if (mp > 0) {
         hipLaunchKernelGGL((als_piece_kernel<D>), dim3((unsigned)mp), dim3(kBlk), 0, st, Y, rowptr, col, val, rows, (int)n_solve, (int)split_len, (int)mp, alpha,
                            (const int32_t *)piece_off, parts);
-        ALS_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL((als_row_kernel<D>), dim3((unsigned)n_solve), dim3(kBlk), 0, st, Y, G, rowptr, col, val, rows, (int)n_solve, (int)mp, alpha, lambda,
                        (const int32_t *)piece_off, (const unsigned char *)parts, X);
-    ALS_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -527,10 +520,10 @@ int arl_als_gram_f64(const float *Y, int64_t n, int64_t d, double *G, void *work
     else if (d == 64) ALS_GRAM(64);
     else ALS_GRAM(128);
 #undef ALS_GRAM
-    ALS_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     const int dd = (int)(d * d);
     hipLaunchKernelGGL(als_gram_fold_kernel, dim3((unsigned)((dd + kBlk - 1) / kBlk)), dim3(kBlk), 0, st, (const double *)part, gs.ns, dd, G);
-    ALS_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -581,16 +574,16 @@ int arl_als_objective_f64(const float *X, int64_t n_rows, const float *Y, int64_
     else if (d == 64) ALS_OBJ(64);
     else ALS_OBJ(128);
 #undef ALS_OBJ
-    ALS_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     const long long ny = (long long)n * d;
     long long parts = (ny + 4095) / 4096;
     if (parts > kSumParts) parts = kSumParts;
     const long long span = (ny + parts - 1) / parts;
     parts = (ny + span - 1) / span;
     hipLaunchKernelGGL(als_sumsq_kernel, dim3((unsigned)parts), dim3(kBlk), 0, st, Y, ny, span, lambda, term + n_rows);
-    ALS_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(als_fold_kernel, dim3(1), dim3(kBlk), 0, st, (const double *)term, (long long)n_rows + parts, out);
-    ALS_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 

@@ -7,9 +7,7 @@
 //     dPu[u] = U T sum_i P[u, i] Pi[i] - I sum_t Pi[c_t],   dPi[i] = U T sum_u P[u, i] Pu[u] - I #{t : c_t = i} sum_u Pu[u].
 //
 // Rules kept throughout:
-//   * scores and the P-weighted row sums run exact fp32 on v_mfma_f32_16x16x4_f32, in the layout of the all-rows InfoNCE kernel: a wave keeps 16
-//     rows of the RESIDENT table in registers, the STREAMED table passes through LDS 64 rows at a time (double-buffered), the scores come out
-//     in the A-operand layout of the second product;
+//   * scores and the P-weighted row sums run exact fp32 on v_mfma_f32_16x16x4_f32 on the shared streamed tile (arl_stream.h);
 //   * three passes: lse (items resident, users streamed in splits, running maximum), dPi (items resident, users streamed in splits), dPu (users
 //     resident, all items streamed, one writer per output row);
 //   * every reduction has a fixed order (lane groups, then splits / row chunks ascending): no atomics, bit-identical from run to run;
@@ -18,18 +16,13 @@
 #include <stdint.h>
 #include <math.h>
 #include "arlib_amd.h"
-
-#define CSM_LAUNCH_CHECK()                                  \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
+#include "arl_stream.h"
 
 namespace {
 
 constexpr int kBlk = 256, kWaves = 4;
 constexpr float kNegBig = -3.0e38f;          // running maximum before any score (finite: exp(kNegBig - m) is 0, never NaN)
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+using strm::f32x4v;
 
 enum { CSM_LSE = 0, CSM_GRAD_LSE_R = 1, CSM_GRAD_LSE_T = 2 };
 
@@ -40,48 +33,33 @@ template <int D, int MODE>
 __global__ __launch_bounds__(kBlk) void csm_stream_kernel(const float *__restrict__ Xr, int nR, const float *__restrict__ Xt, int nT, int split_len,
                                                            const float *__restrict__ lse, float scale, const float *__restrict__ sub_vec,
                                                            float *__restrict__ out, float *__restrict__ pm, float *__restrict__ ps) {
-    constexpr int Q = D / 4, LD = D + 4, NT = D / 16;
+    constexpr int NT = D / 16;
     constexpr bool GRAD = MODE != CSM_LSE;
-    __shared__ float tile[2][64 * LD];
+    __shared__ float tile[2][strm::kStageFloats<D>];
     __shared__ float tlse[2][64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, g = lane >> 4;
     const int r0 = (blockIdx.x * kWaves + wv) * 16;
     const int t_begin = blockIdx.y * split_len, t_end = min(nT, t_begin + split_len);
-    float br[Q];
-    {
-        const int r = r0 + c;
-#pragma unroll
-        for (int i = 0; i < Q; i += 4) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < nR) v = *reinterpret_cast<const float4 *>(Xr + (size_t)r * D + Q * g + i);
-            br[i] = v.x; br[i + 1] = v.y; br[i + 2] = v.z; br[i + 3] = v.w;
-        }
-    }
+    float br[D / 4];
+    strm::load_resident<D>(Xr, r0 + c, nR, g, br);
     const float lse_r = (MODE == CSM_GRAD_LSE_R && r0 + c < nR) ? lse[r0 + c] : 0.f;
     f32x4v o[NT];
 #pragma unroll
     for (int n = 0; n < NT; ++n) o[n] = f32x4v{0.f, 0.f, 0.f, 0.f};
     float m = kNegBig, sum = 0.f;
     const int nst = (t_end - t_begin + 63) / 64;
-    // a stage is 64 x D floats = 16 D float4s over 256 threads; the NEXT stage is fetched into registers before the current one is consumed
-    // and goes to the other LDS buffer afterwards (macros, not lambdas: an array captured by reference stays in scratch memory)
-    constexpr int PF = 64 * (D / 4) / kBlk;
-    f32x4v pre[PF];
+    // beside a stage's rows: the streamed rows' lse (CSM_GRAD_LSE_T), fetched and stashed with them
+    strm::stage<D> stg(tid);
     float pre_lse = 0.f;
-    const int frow = tid / (D / 4), fq = (tid % (D / 4)) * 4;
-    constexpr int FSTEP = kBlk / (D / 4);
-#define CSM_FETCH(ST)                                                                                                              \
-    do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) {                                                                           \
-            const int t = min(t_begin + (ST) * 64 + frow + i * FSTEP, nT - 1);     /* clamped; rows past t_end are masked below */ \
-            pre[i] = *reinterpret_cast<const f32x4v *>(Xt + (size_t)t * D + fq);                                                   \
-        }                                                                                                                          \
-        if (MODE == CSM_GRAD_LSE_T && tid < 64) pre_lse = lse[min(t_begin + (ST) * 64 + tid, nT - 1)];                             \
+#define CSM_FETCH(ST)                                                                                  \
+    do {                                                                                               \
+        stg.fetch(Xt, t_begin + (ST) * 64, nT);                                                        \
+        if (MODE == CSM_GRAD_LSE_T && tid < 64) pre_lse = lse[min(t_begin + (ST) * 64 + tid, nT - 1)]; \
     } while (0)
-#define CSM_STASH(BUF)                                                                                                             \
-    do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) *reinterpret_cast<f32x4v *>(&tile[BUF][(frow + i * FSTEP) * LD + fq]) = pre[i]; \
-        if (MODE == CSM_GRAD_LSE_T && tid < 64) tlse[BUF][tid] = pre_lse;                                                          \
+#define CSM_STASH(BUF)                                                    \
+    do {                                                                  \
+        stg.stash(tile[BUF]);                                             \
+        if (MODE == CSM_GRAD_LSE_T && tid < 64) tlse[BUF][tid] = pre_lse; \
     } while (0)
     if (nst > 0) { CSM_FETCH(0); CSM_STASH(0); }
     __syncthreads();
@@ -91,16 +69,7 @@ __global__ __launch_bounds__(kBlk) void csm_stream_kernel(const float *__restric
         const float *T = tile[buf];
 #pragma unroll
         for (int sub = 0; sub < 4; ++sub) {
-            f32x4v sc = f32x4v{0.f, 0.f, 0.f, 0.f};
-            const float *arow = T + (sub * 16 + c) * LD + Q * g;
-#pragma unroll
-            for (int i = 0; i < Q; i += 4) {
-                const float4 a = *reinterpret_cast<const float4 *>(arow + i);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, br[i], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, br[i + 1], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, br[i + 2], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, br[i + 3], sc, 0, 0, 0);
-            }
+            const f32x4v sc = strm::scores<D>(strm::a_row<D>(T, sub, c, g), br);
             const int tb = t_begin + st * 64 + sub * 16 + 4 * g;        // streamed row of register 0
             if (!GRAD) {
                 float mx = m;
@@ -119,12 +88,7 @@ __global__ __launch_bounds__(kBlk) void csm_stream_kernel(const float *__restric
                     const float l = MODE == CSM_GRAD_LSE_R ? lse_r : tlse[buf][sub * 16 + 4 * g + j];
                     pj[j] = tb + j < t_end ? expf(sc[j] - l) : 0.f;
                 }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float *brow = T + (sub * 16 + 4 * g + j) * LD + c;
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(pj[j], brow[16 * n], o[n], 0, 0, 0);
-                }
+                strm::accumulate<D>(T, sub, c, g, pj, o);
             }
         }
         if (st + 1 < nst) CSM_STASH(buf ^ 1);
@@ -146,15 +110,15 @@ __global__ __launch_bounds__(kBlk) void csm_stream_kernel(const float *__restric
             pm[(size_t)blockIdx.y * nR + r0 + c] = m;
             ps[(size_t)blockIdx.y * nR + r0 + c] = sum;
         }
+    } else if (MODE == CSM_GRAD_LSE_R) {
+        strm::store_partial<D>(out, blockIdx.y, nR, r0, g, c, o);
     } else {
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
                 const int r = r0 + 4 * g + reg;
-                if (r >= nR) continue;
-                if (MODE == CSM_GRAD_LSE_T) out[(size_t)r * D + 16 * n + c] = scale * o[n][reg] - sub_vec[16 * n + c];
-                else out[((size_t)blockIdx.y * nR + r) * D + 16 * n + c] = o[n][reg];
+                if (r < nR) out[(size_t)r * D + 16 * n + c] = scale * o[n][reg] - sub_vec[16 * n + c];
             }
     }
 }
@@ -248,22 +212,10 @@ __global__ __launch_bounds__(kBlk) void csm_fold_items_kernel(const float4 *__re
     }
 }
 
-// splits of the streamed table when nR rows are resident: enough workgroups to fill the chip several times over, at least 4 096 streamed rows each
-int csm_splits(int64_t nR, int64_t nT) {
-    const int64_t row_blocks = (nR + 63) / 64;
-    int64_t s = (2048 + row_blocks - 1) / row_blocks;
-    const int64_t max_s = (nT + 4095) / 4096;
-    if (s > max_s) s = max_s;
-    if (s > 256) s = 256;
-    return (int)(s < 1 ? 1 : s);
-}
-
 int csm_chunks(int64_t U) {
     const int64_t c = (U + 1023) / 1024;
     return (int)(c > 1024 ? 1024 : (c < 1 ? 1 : c));
 }
-
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 struct CsmLayout {
     size_t colpart, head, lpart, sub_u, sub_i, pm, ps, gpart, total;
@@ -272,7 +224,7 @@ struct CsmLayout {
 
 CsmLayout csm_layout(int64_t U, int64_t I, int64_t d, bool want_dPi) {
     CsmLayout L;
-    L.ns = csm_splits(I, U);
+    L.ns = strm::split_count(I, U);
     L.chunks = csm_chunks(U);
     L.lblocks = (int)((I + kBlk - 1) / kBlk);
     size_t o = 0;
@@ -297,34 +249,34 @@ int csm_run(const float *Pu, int64_t U, const float *Pi, int64_t I, const int32_
     float *gpart = (float *)(ws + L.gpart);
     const long long chunk = (U + L.chunks - 1) / L.chunks;
     hipLaunchKernelGGL(csm_colsum_partial_kernel, dim3((unsigned)L.chunks), dim3(kBlk), 0, st, Pu, (long long)U, D, chunk, colpart);
-    CSM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(csm_head_kernel, dim3(1), dim3(kBlk), 0, st, colpart, L.chunks, Pi, targets, (int)T, D, (double)I, head, sub_u, sub_i);
-    CSM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     const int split_len = (int)((U + L.ns - 1) / L.ns);
     const dim3 grid_items((unsigned)((I + 63) / 64), (unsigned)L.ns);
     hipLaunchKernelGGL((csm_stream_kernel<D, CSM_LSE>), grid_items, dim3(kBlk), 0, st, Pi, (int)I, Pu, (int)U, split_len, (const float *)nullptr, 0.f,
                        (const float *)nullptr, (float *)nullptr, pm, ps);
-    CSM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(csm_lse_finish_kernel, dim3((unsigned)L.lblocks), dim3(kBlk), 0, st, pm, ps, L.ns, (int)I, lse, lpart);
-    CSM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(csm_loss_kernel, dim3(1), dim3(kBlk), 0, st, head, lpart, L.lblocks, (double)U, (double)I, (double)T, loss);
-    CSM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     const float scale = (float)((double)U * (double)T);
     if (dPi) {
         hipLaunchKernelGGL((csm_stream_kernel<D, CSM_GRAD_LSE_R>), grid_items, dim3(kBlk), 0, st, Pi, (int)I, Pu, (int)U, split_len, (const float *)lse, 0.f,
                            (const float *)nullptr, gpart, (float *)nullptr, (float *)nullptr);
-        CSM_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
         const long long n4 = I * (D / 4);
         long long blocks = (n4 + kBlk - 1) / kBlk;
         if (blocks > 65535) blocks = 65535;
         hipLaunchKernelGGL(csm_fold_items_kernel, dim3((unsigned)blocks), dim3(kBlk), 0, st, (const float4 *)gpart, L.ns, (int)I, D / 4, scale, targets, (int)T,
                            (const float *)sub_i, (float4 *)dPi);
-        CSM_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
     }
     if (dPu) {
         hipLaunchKernelGGL((csm_stream_kernel<D, CSM_GRAD_LSE_T>), dim3((unsigned)((U + 63) / 64), 1u), dim3(kBlk), 0, st, Pu, (int)U, Pi, (int)I, (int)I,
                            (const float *)lse, scale, (const float *)sub_u, dPu, (float *)nullptr, (float *)nullptr);
-        CSM_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
     }
     return ARL_OK;
 }
@@ -347,10 +299,9 @@ int arl_colsoftmax_target_loss_f32(const float *Pu, int64_t U, const float *Pi, 
     if (((uintptr_t)Pu | (uintptr_t)Pi | (uintptr_t)dPu | (uintptr_t)dPi | (uintptr_t)workspace) & 15) return ARL_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    if (d == 16) return csm_run<16>(Pu, U, Pi, I, targets, T, lse, loss, dPu, dPi, ws, st);
-    if (d == 32) return csm_run<32>(Pu, U, Pi, I, targets, T, lse, loss, dPu, dPi, ws, st);
-    if (d == 64) return csm_run<64>(Pu, U, Pi, I, targets, T, lse, loss, dPu, dPi, ws, st);
-    return csm_run<128>(Pu, U, Pi, I, targets, T, lse, loss, dPu, dPi, ws, st);
+#define CSM_RUN(DD) return csm_run<DD>(Pu, U, Pi, I, targets, T, lse, loss, dPu, dPi, ws, st)
+    ARL_DISPATCH_WIDTH(d, CSM_RUN);
+#undef CSM_RUN
 }
 
 }  // extern "C"

@@ -12,12 +12,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "arlib_amd.h"
-
-#define GAN_LAUNCH_CHECK()                                  \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
+#include "arl_util.h"
 
 namespace {
 
@@ -249,14 +244,8 @@ __global__ __launch_bounds__(kBlk) void gan_fold_kernel(const float *__restrict_
 
 // ------------------------------------------------------------------------------------------------ template
 // Counter hash of (seed, call, row, item) -> uniform in [0, 1) with 24 bits (splitmix64 finaliser).
-__device__ __forceinline__ uint64_t smix(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __device__ __forceinline__ bool hash_keep(uint64_t key, long long r, long long item, float p) {
-    const uint64_t u = smix(key ^ ((uint64_t)r * 0x100000000ull + (uint64_t)item)) >> 40;
+    const uint64_t u = arl_splitmix64(key ^ ((uint64_t)r * 0x100000000ull + (uint64_t)item)) >> 40;
     return (float)u * (1.f / 16777216.f) < p;
 }
 
@@ -350,7 +339,7 @@ int launch_gemm(int M, int N, int K, const float *A, long long sam, long long sa
     else if (bnc) GAN_GEMM_LAUNCH(false, true);
     else GAN_GEMM_LAUNCH(false, false);
 #undef GAN_GEMM_LAUNCH
-    GAN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -382,7 +371,7 @@ int arl_gan_spmm_f32(int64_t n_rows, int64_t N, const int64_t *rowptr, const int
     if (n_rows == 0 || N == 0) return ARL_OK;
     hipLaunchKernelGGL(gan_spmm_kernel, dim3((unsigned)n_rows, cdiv(N, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, (int)n_rows, (int)N, rowptr, col, val, X, bias,
                        (int)relu, out);
-    GAN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -392,7 +381,7 @@ int arl_gan_transpose_f32(const float *A, int64_t R, int64_t Cn, float *At, arl_
     if (R * Cn > kGanMaxElems) return ARL_E_RANGE;
     if (R == 0 || Cn == 0) return ARL_OK;
     hipLaunchKernelGGL(gan_transpose_kernel, dim3(cdiv(Cn, 32), cdiv(R, 32)), dim3(kBlk), 0, (hipStream_t)stream, A, (int)R, (int)Cn, At);
-    GAN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -403,9 +392,9 @@ int arl_gan_rows_f32(const float *Y, const float *Td, int64_t F, int64_t S, int6
     if (F * S > kGanMaxElems) return ARL_E_RANGE;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(gan_rows_kernel, dim3((unsigned)F), dim3(kBlk), 0, st, Y, Td, (int)S, (int)T, wD, rows);
-    GAN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(gan_loss_kernel, dim3(1), dim3(kBlk), 0, st, rows, (int)F, (int)S, bD, losses, coef, pf);
-    GAN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -415,7 +404,7 @@ int arl_gan_dz2_f32(const float *Y, const float *Td, const float *rows, const fl
     if (F < 1 || S < 1 || T < 0 || T > S) return ARL_E_ARG;
     if (F * S > kGanMaxElems) return ARL_E_RANGE;
     hipLaunchKernelGGL(gan_dz2_kernel, dim3((unsigned)F), dim3(kBlk), 0, (hipStream_t)stream, Y, Td, rows, pf, wD, (int)F, (int)S, (int)T, dZ2);
-    GAN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -435,19 +424,14 @@ int arl_gan_colsum_f32(const float *A, const float *wa, const float *Bm, const f
     hipStream_t st = (hipStream_t)stream;
     float *part = (float *)workspace;
     hipLaunchKernelGGL(gan_colsum_kernel, dim3(cdiv(S, kBlk), (unsigned)n_part), dim3(kBlk), 0, st, A, wa, Bm, wb, (int)F, (int)S, chunk, part);
-    GAN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(gan_fold_kernel, dim3(cdiv(S, kBlk)), dim3(kBlk), 0, st, part, n_part, (int)S, out);
-    GAN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
-uint64_t arl_gan_hash_key(uint64_t seed, uint64_t call) {
-    uint64_t x = seed ^ (call * 0x9E3779B97F4A7C15ull);
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+// the key of a call: one hash of (seed, call), shared by every kernel of the library that draws from the counter hash
+uint64_t arl_gan_hash_key(uint64_t seed, uint64_t call) { return arl_splitmix64(seed ^ (call * 0x9E3779B97F4A7C15ull)); }
 
 int arl_gan_template_i32(int64_t F, int64_t S, int64_t n_users, const int32_t *user_set, const int64_t *rowptr, const int32_t *col, const float *val,
                          const int32_t *pos, const int32_t *items, const uint8_t *mask, const float *item_p, uint64_t seed, uint64_t call,
@@ -461,7 +445,7 @@ int arl_gan_template_i32(int64_t F, int64_t S, int64_t n_users, const int32_t *u
     GanTemplateArgs a{(int)F, (int)S, (int)n_users, user_set, rowptr, col, val, pos, items, mask, item_p, arl_gan_hash_key(seed, call), out_ptr, counts,
                       out_col, out_val};
     hipLaunchKernelGGL(gan_template_kernel, dim3(cdiv(F, kBlk / 64)), dim3(kBlk), 0, (hipStream_t)stream, a);
-    GAN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -473,7 +457,7 @@ int arl_gan_hash_mask_u8(int64_t F, int64_t S, const int32_t *items, const float
     if (F == 0) return ARL_OK;
     hipLaunchKernelGGL(gan_hash_mask_kernel, dim3(cdiv(F * S, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, (int)F, (int)S, items, item_p,
                        arl_gan_hash_key(seed, call), out);
-    GAN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -485,7 +469,7 @@ int arl_gan_threshold_f32(const float *Y, int64_t F, int64_t S, float thr, const
     if (F == 0) return ARL_OK;
     hipLaunchKernelGGL(gan_threshold_kernel, dim3(cdiv(F, kBlk / 64)), dim3(kBlk), 0, (hipStream_t)stream, Y, (int)F, (int)S, thr, out_ptr, counts,
                        out_col);
-    GAN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 

@@ -13,14 +13,9 @@
 #include <math.h>
 #include <stdio.h>
 #include "arlib_amd.h"
+#include "arl_stream.h"
 #include "arl_ordered.h"
 #include <type_traits>
-
-#define ARL_LAUNCH_CHECK()                                  \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
 
 namespace {
 
@@ -1360,49 +1355,34 @@ __global__ __launch_bounds__(kBlock) void nce_grad_kernel(const float *__restric
 template <int D, bool GRAD, bool LSE_ON_R, bool FUSED = false>
 __global__ __launch_bounds__(kBlock) void nce_allrows_kernel(const float *__restrict__ Xr, int nR, const float *__restrict__ Xt, int nT, int split_len,
                                                               float inv_tau, const float *__restrict__ lse, float *__restrict__ out, float *__restrict__ sums) {
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    constexpr int Q = D / 4, LD = D + 4, NT = D / 16;
-    __shared__ float tile[2][64 * LD];
+    typedef strm::f32x4v v4f;
+    constexpr int NT = D / 16;
+    static_assert(kBlock == strm::kThreads, "the streamed tile is staged by 256 threads");
+    __shared__ float tile[2][strm::kStageFloats<D>];
     __shared__ float tlse[2][64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, g = lane >> 4;
     const int r0 = (blockIdx.x * kWavesPerBlock + wv) * 16;
     const int t_begin = blockIdx.y * split_len, t_end = min(nT, t_begin + split_len);
-    float br[Q];
-    {
-        const int r = r0 + c;
-#pragma unroll
-        for (int i = 0; i < Q; i += 4) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < nR) v = *reinterpret_cast<const float4 *>(Xr + (size_t)r * D + Q * g + i);
-            br[i] = v.x; br[i + 1] = v.y; br[i + 2] = v.z; br[i + 3] = v.w;
-        }
-    }
+    float br[D / 4];
+    strm::load_resident<D>(Xr, r0 + c, nR, g, br);
     const float lse_r = (GRAD && LSE_ON_R && !FUSED && r0 + c < nR) ? lse[r0 + c] : 0.f;
     v4f o[NT];
 #pragma unroll
     for (int n = 0; n < NT; ++n) o[n] = v4f{0.f, 0.f, 0.f, 0.f};
     float sum = 0.f;
     const int nst = (t_end - t_begin + 63) / 64;
-    // staging: a stage is 64 x D floats = 16 D float4s over 256 threads; the NEXT stage is fetched into registers before the current one
-    // is consumed and goes to the other LDS buffer afterwards (its last readers passed the barrier of the stage before)
-    // (macros, not lambdas: an array captured by reference stays in scratch memory and every load is waited for at once)
-    constexpr int PF = 64 * (D / 4) / kBlock;
-    v4f pre[PF];
+    // beside a stage's rows: the streamed rows' lse (GRAD, !LSE_ON_R), fetched and stashed with them
+    strm::stage<D> stg(tid);
     float pre_lse = 0.f;
-    const int frow = tid / (D / 4), fq = (tid % (D / 4)) * 4;               // this thread's row (+ i * kBlock / (D/4)) and column of a stage
-    constexpr int FSTEP = kBlock / (D / 4);
-#define ARL_NCE_FETCH(ST)                                                                                                          \
-    do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) {                                                                           \
-            const int t = min(t_begin + (ST) * 64 + frow + i * FSTEP, nT - 1);     /* clamped; rows past t_end are masked below */ \
-            pre[i] = *reinterpret_cast<const v4f *>(Xt + (size_t)t * D + fq);                                                      \
-        }                                                                                                                          \
-        if (GRAD && !LSE_ON_R && tid < 64) pre_lse = lse[min(t_begin + (ST) * 64 + tid, nT - 1)];                                  \
+#define ARL_NCE_FETCH(ST)                                                                         \
+    do {                                                                                          \
+        stg.fetch(Xt, t_begin + (ST) * 64, nT);                                                   \
+        if (GRAD && !LSE_ON_R && tid < 64) pre_lse = lse[min(t_begin + (ST) * 64 + tid, nT - 1)]; \
     } while (0)
-#define ARL_NCE_STASH(BUF)                                                                                                         \
-    do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) *reinterpret_cast<v4f *>(&tile[BUF][(frow + i * FSTEP) * LD + fq]) = pre[i]; \
-        if (GRAD && !LSE_ON_R && tid < 64) tlse[BUF][tid] = pre_lse;                                                               \
+#define ARL_NCE_STASH(BUF)                                           \
+    do {                                                             \
+        stg.stash(tile[BUF]);                                        \
+        if (GRAD && !LSE_ON_R && tid < 64) tlse[BUF][tid] = pre_lse; \
     } while (0)
     if (nst > 0) { ARL_NCE_FETCH(0); ARL_NCE_STASH(0); }
     __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0): the resident rows have landed on every path into the loop (else the in-loop wait is vmcnt(0) too)
@@ -1413,16 +1393,7 @@ __global__ __launch_bounds__(kBlock) void nce_allrows_kernel(const float *__rest
         const float *T = tile[buf];
 #pragma unroll
         for (int sub = 0; sub < 4; ++sub) {
-            v4f sc = v4f{0.f, 0.f, 0.f, 0.f};
-            const float *arow = T + (sub * 16 + c) * LD + Q * g;
-#pragma unroll
-            for (int i = 0; i < Q; i += 4) {
-                const float4 a = *reinterpret_cast<const float4 *>(arow + i);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, br[i], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, br[i + 1], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, br[i + 2], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, br[i + 3], sc, 0, 0, 0);
-            }
+            const v4f sc = strm::scores<D>(strm::a_row<D>(T, sub, c, g), br);
             const int tb = t_begin + st * 64 + sub * 16 + 4 * g;        // streamed row of register 0
             float pj[4];
 #pragma unroll
@@ -1432,14 +1403,7 @@ __global__ __launch_bounds__(kBlock) void nce_allrows_kernel(const float *__rest
                 else pj[j] = ok ? __expf(sc[j] * inv_tau - (LSE_ON_R ? lse_r : tlse[buf][sub * 16 + 4 * g + j])) : 0.f;
             }
             if (!GRAD || FUSED) sum += (pj[0] + pj[1]) + (pj[2] + pj[3]);
-            if (GRAD) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float *brow = T + (sub * 16 + 4 * g + j) * LD + c;
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(pj[j], brow[16 * n], o[n], 0, 0, 0);
-                }
-            }
+            if (GRAD) strm::accumulate<D>(T, sub, c, g, pj, o);
         }
         if (st + 1 < nst) ARL_NCE_STASH(buf ^ 1);
         __syncthreads();
@@ -1450,15 +1414,7 @@ __global__ __launch_bounds__(kBlock) void nce_allrows_kernel(const float *__rest
         sum += __shfl_xor(sum, 16); sum += __shfl_xor(sum, 32);         // over the four lane groups (fixed order)
         if (g == 0 && r0 + c < nR) (GRAD ? sums : out)[(size_t)blockIdx.y * nR + r0 + c] = sum;
     }
-    if (GRAD) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int r = r0 + 4 * g + reg;
-                if (r < nR) out[((size_t)blockIdx.y * nR + r) * D + 16 * n + c] = o[n][reg];
-            }
-    }
+    if (GRAD) strm::store_partial<D>(out, blockIdx.y, nR, r0, g, c, o);
 }
 
 // lse[b] = 1/T + log(sum over splits of the partial sums), splits added in order
@@ -2125,12 +2081,6 @@ __global__ __launch_bounds__(kBlock) void simgcl_perturb_kernel(float *__restric
 // (seed, stream, row_id * d + k) -- what torch.rand_like(ego) supplies in recommender/SimGCL.py:203-205, without materialising an
 // [N, d] noise table, a clone of the operand, or a second pass.  dst may alias src.  row_ids (optional): the operand holds the listed
 // rows of a larger table and gets exactly the noise those rows would get in a full-table call with the same (seed, stream).
-__device__ __forceinline__ unsigned long long arl_splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __global__ __launch_bounds__(kBlock) void simgcl_perturb_rng_kernel(const float *__restrict__ src, float *__restrict__ dst, int n, int d,
                                                                      const int32_t *__restrict__ row_ids, float eps, unsigned long long key) {
     const int lane = threadIdx.x & 63;
@@ -4977,8 +4927,7 @@ int arl_simgcl_perturb_rng_f32(const float *src, float *dst, int64_t n, int64_t 
     if (d <= 0 || d > 256) return ARL_E_DIM;
     if (n < 0 || n > 0x7fffffffll) return ARL_E_ARG;
     if (n == 0) return ARL_OK;
-    unsigned long long key = seed ^ (stream_id * 0x9E3779B97F4A7C15ull);          // one hash of (seed, stream) keys the whole call
-    key += 0x9E3779B97F4A7C15ull; key = (key ^ (key >> 30)) * 0xBF58476D1CE4E5B9ull; key = (key ^ (key >> 27)) * 0x94D049BB133111EBull; key ^= key >> 31;
+    const unsigned long long key = arl_gan_hash_key(seed, stream_id);             // one hash of (seed, stream) keys the whole call
     hipLaunchKernelGGL(simgcl_perturb_rng_kernel, dim3((unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, (hipStream_t)stream, src, dst,
                        (int)n, (int)d, row_ids, eps, key);
     ARL_LAUNCH_CHECK();
@@ -5018,8 +4967,7 @@ int arl_ssl_dropout_nce_f32(const float *Xu, const float *Xp, int64_t n, int64_t
     if (n <= 0 || n > 0x7fffffffll / 128 || !(p >= 0.f && p < 1.f) || !(tau >= 0.023f)) return ARL_E_ARG;     // tau: the all-rows kernels' fixed shift
     if (((uintptr_t)Xu | (uintptr_t)Xp | (uintptr_t)Gu | (uintptr_t)Gp | (uintptr_t)workspace) & 15) return ARL_E_ARG;
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long key = seed ^ (stream_id * 0x9E3779B97F4A7C15ull);          // the same (seed, stream) hash as arl_simgcl_perturb_rng_f32
-    key += 0x9E3779B97F4A7C15ull; key = (key ^ (key >> 30)) * 0xBF58476D1CE4E5B9ull; key = (key ^ (key >> 27)) * 0x94D049BB133111EBull; key ^= key >> 31;
+    const unsigned long long key = arl_gan_hash_key(seed, stream_id);             // the same (seed, stream) hash as arl_simgcl_perturb_rng_f32
     const int ni = (int)n;
     const int64_t n4 = (n + 3) & ~3ll, nd = n * d;
     const int ns = ssl_nce_splits(n);

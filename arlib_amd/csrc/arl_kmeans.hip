@@ -5,9 +5,9 @@
 // update: C[c] = mean of the rows labelled c.  The inertia of an assign pass is  sum_n |x_n|^2 - 2 sum_n best[n].
 //
 // Rules kept throughout:
-//   * the N x k scores are never stored: products run exact fp32 on v_mfma_f32_16x16x4_f32 in the layout of the all-rows InfoNCE kernel and of
-//     csm_stream_kernel: a wave keeps 16 POINTS in registers, the CENTROIDS and their bias -1/2 |c|^2 pass through LDS 64 rows at a time
-//     (double-buffered), every lane keeps a running (best, index) over the centroids it sees, the four lanes of a point reduce at the end;
+//   * the N x k scores are never stored: products run exact fp32 on v_mfma_f32_16x16x4_f32 on the shared streamed tile (arl_stream.h): the POINTS
+//     are resident, the CENTROIDS and their bias -1/2 |c|^2 are streamed, every lane keeps a running (best, index) over the centroids it sees,
+//     the four lanes of a point reduce at the end;
 //   * ties go to the LOWER centroid index: a lane meets its centroids in ascending order and replaces its best only on a strict >, the
 //     cross-lane reduce prefers the lower index on equal scores;
 //   * the running index starts at 0, so a point whose scores are all NaN gets label 0 -- labels index the centroid table, never out of range;
@@ -18,19 +18,14 @@
 #include <stdint.h>
 #include <math.h>
 #include "arlib_amd.h"
-
-#define KM_LAUNCH_CHECK()                                   \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
+#include "arl_stream.h"
 
 namespace {
 
 constexpr int kBlk = 256, kWaves = 4;
 constexpr int kChunk = 256;                  // member rows per partial sum of the update
 constexpr int kSumParts = 1024;              // spans of the double sums
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+using strm::f32x4v;
 
 // bias[c] = -1/2 |C[c]|^2, one thread per centroid, components in order
 __global__ __launch_bounds__(kBlk) void km_bias_kernel(const float *__restrict__ C, int K, int d, float *__restrict__ bias) {
@@ -49,68 +44,35 @@ __global__ __launch_bounds__(kBlk) void km_bias_kernel(const float *__restrict__
 template <int D>
 __global__ __launch_bounds__(kBlk) void km_assign_kernel(const float *__restrict__ X, int N, const float *__restrict__ Cn, const float *__restrict__ bias, int K,
                                                           int32_t *__restrict__ labels, float *__restrict__ score) {
-    constexpr int Q = D / 4, LD = D + 4;
-    __shared__ __attribute__((aligned(16))) float tile[2][64 * LD];
+    __shared__ __attribute__((aligned(16))) float tile[2][strm::kStageFloats<D>];
     __shared__ __attribute__((aligned(16))) float tbias[2][64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, g = lane >> 4;
     const int r0 = (blockIdx.x * kWaves + wv) * 16;
-    float br[Q];
-    {
-        const int r = r0 + c;
-#pragma unroll
-        for (int i = 0; i < Q; i += 4) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < N) v = *reinterpret_cast<const float4 *>(X + (size_t)r * D + Q * g + i);
-            br[i] = v.x; br[i + 1] = v.y; br[i + 2] = v.z; br[i + 3] = v.w;
-        }
-    }
+    float br[D / 4];
+    strm::load_resident<D>(X, r0 + c, N, g, br);
     float best = -INFINITY;
     int bi = 0;
     const int nst = (K + 63) / 64;
-    // a stage is 64 x D floats = 16 D float4s over 256 threads; the NEXT stage is fetched into registers before the current one is consumed
-    // and goes to the other LDS buffer afterwards (macros, not lambdas: an array captured by reference stays in scratch memory)
-    constexpr int PF = 64 * (D / 4) / kBlk;
-    f32x4v pre[PF];
+    // beside a stage's centroids: their bias, fetched and stashed with them
+    strm::stage<D> stg(tid);
     float pre_b = 0.f;
-    const int frow = tid / (D / 4), fq = (tid % (D / 4)) * 4;
-    constexpr int FSTEP = kBlk / (D / 4);
-#define KM_FETCH(ST)                                                                                                               \
-    do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) {                                                                           \
-            const int t = min((ST) * 64 + frow + i * FSTEP, K - 1);               /* clamped; rows past K are masked below */      \
-            pre[i] = *reinterpret_cast<const f32x4v *>(Cn + (size_t)t * D + fq);                                                   \
-        }                                                                                                                          \
-        if (tid < 64) pre_b = bias[min((ST) * 64 + tid, K - 1)];                                                                   \
+#define KM_FETCH(ST)                                             \
+    do {                                                         \
+        stg.fetch(Cn, (ST) * 64, K);                             \
+        if (tid < 64) pre_b = bias[min((ST) * 64 + tid, K - 1)]; \
     } while (0)
-#define KM_STASH(BUF)                                                                                                              \
-    do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) *reinterpret_cast<f32x4v *>(&tile[BUF][(frow + i * FSTEP) * LD + fq]) = pre[i]; \
-        if (tid < 64) tbias[BUF][tid] = pre_b;                                                                                     \
+#define KM_STASH(BUF)                          \
+    do {                                       \
+        stg.stash(tile[BUF]);                  \
+        if (tid < 64) tbias[BUF][tid] = pre_b; \
     } while (0)
     KM_FETCH(0); KM_STASH(0);
     __syncthreads();
     for (int st = 0; st < nst; ++st) {
         const int buf = st & 1;
         if (st + 1 < nst) KM_FETCH(st + 1);
-        const float *T = tile[buf] + c * LD + Q * g;
-        // the stage's four 16-centroid tiles on four independent accumulators (the 16x16x4 form needs >= 2 to reach its issue rate)
-        f32x4v sc[4];
-#pragma unroll
-        for (int sub = 0; sub < 4; ++sub) sc[sub] = f32x4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < Q; i += 4) {
-            float4 a[4];
-#pragma unroll
-            for (int sub = 0; sub < 4; ++sub) a[sub] = *reinterpret_cast<const float4 *>(T + sub * 16 * LD + i);
-#pragma unroll
-            for (int sub = 0; sub < 4; ++sub) sc[sub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[sub].x, br[i], sc[sub], 0, 0, 0);
-#pragma unroll
-            for (int sub = 0; sub < 4; ++sub) sc[sub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[sub].y, br[i + 1], sc[sub], 0, 0, 0);
-#pragma unroll
-            for (int sub = 0; sub < 4; ++sub) sc[sub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[sub].z, br[i + 2], sc[sub], 0, 0, 0);
-#pragma unroll
-            for (int sub = 0; sub < 4; ++sub) sc[sub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[sub].w, br[i + 3], sc[sub], 0, 0, 0);
-        }
+        f32x4v sc[4];                                                    // the stage's four 16-centroid tiles
+        strm::scores4<D>(tile[buf], c, g, br, sc);
         // register j of tile sub is centroid st * 64 + sub * 16 + 4 g + j against point r0 + c: ascending in (sub, j), so a strict > keeps the lower index
 #pragma unroll
         for (int sub = 0; sub < 4; ++sub) {
@@ -397,8 +359,6 @@ __global__ __launch_bounds__(kPickBlk) void kpp_pick_kernel(const float *__restr
     if (lane == 0) next_ids[wv] = kpp_clamp(id, N);
 }
 
-bool km_width(int64_t d) { return d == 16 || d == 32 || d == 64 || d == 128; }
-
 bool km_rows(int64_t n) { return n <= 0x7fffffffll / 128; }
 
 template <int D>
@@ -412,16 +372,15 @@ int kpp_dist_run(const float *X, int64_t N, const int32_t *cand_ids, int id0, in
     else if (T <= 12) KPP_DIST(12);
     else KPP_DIST(16);
 #undef KPP_DIST
-    KM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
 int kpp_dist(const float *X, int64_t N, int64_t d, const int32_t *cand_ids, int id0, int T, const float *closest_base, const int32_t *sel, int n_sel, float *mins,
              double *part, hipStream_t st) {
-    if (d == 16) return kpp_dist_run<16>(X, N, cand_ids, id0, T, closest_base, sel, n_sel, mins, part, st);
-    if (d == 32) return kpp_dist_run<32>(X, N, cand_ids, id0, T, closest_base, sel, n_sel, mins, part, st);
-    if (d == 64) return kpp_dist_run<64>(X, N, cand_ids, id0, T, closest_base, sel, n_sel, mins, part, st);
-    return kpp_dist_run<128>(X, N, cand_ids, id0, T, closest_base, sel, n_sel, mins, part, st);
+#define KPP_RUN(DD) return kpp_dist_run<DD>(X, N, cand_ids, id0, T, closest_base, sel, n_sel, mins, part, st)
+    ARL_DISPATCH_WIDTH(d, KPP_RUN);
+#undef KPP_RUN
 }
 
 int kpp_pick(const float *mins, const double *part, int64_t N, int T, const int32_t *cand_ids, int id0, const double *u, int T_next, int32_t *next_ids,
@@ -429,7 +388,7 @@ int kpp_pick(const float *mins, const double *part, int64_t N, int T, const int3
     const int span = kpp_span(N), S = (int)((N + span - 1) / span);
     hipLaunchKernelGGL(kpp_pick_kernel, dim3(1), dim3(kPickBlk), 0, st, mins, part, (int)N, S, span, T, cand_ids, id0, u, T_next, next_ids, sel_out, index_out,
                        trace_ids, trace_pot, closest_out);
-    KM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -440,9 +399,9 @@ int64_t kpp_part_bytes(int64_t N, int64_t T) { return ((int64_t)sizeof(double) *
 template <int D>
 int km_assign_run(const float *X, int64_t N, const float *C, int64_t k, float *bias, int32_t *labels, float *score, hipStream_t st) {
     hipLaunchKernelGGL(km_bias_kernel, dim3((unsigned)((k + kBlk - 1) / kBlk)), dim3(kBlk), 0, st, C, (int)k, D, bias);
-    KM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL((km_assign_kernel<D>), dim3((unsigned)((N + 63) / 64)), dim3(kBlk), 0, st, X, (int)N, C, (const float *)bias, (int)k, labels, score);
-    KM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -452,37 +411,36 @@ extern "C" {
 
 int arl_kmeans_assign_f32(const float *X, int64_t N, const float *C, int64_t k, int64_t d, float *bias, int32_t *labels, float *score, arl_stream_t stream) {
     if (!X || !C || !bias || !labels || !score) return ARL_E_NULL;
-    if (!km_width(d)) return ARL_E_DIM;
+    if (!arl_width_ok(d)) return ARL_E_DIM;
     if (N <= 0 || k <= 0) return ARL_E_ARG;
     if (N > 0x7fffffffll / 128 || k > 0x7fffffffll / 128) return ARL_E_RANGE;
     if (((uintptr_t)X | (uintptr_t)C) & 15) return ARL_E_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (d == 16) return km_assign_run<16>(X, N, C, k, bias, labels, score, st);
-    if (d == 32) return km_assign_run<32>(X, N, C, k, bias, labels, score, st);
-    if (d == 64) return km_assign_run<64>(X, N, C, k, bias, labels, score, st);
-    return km_assign_run<128>(X, N, C, k, bias, labels, score, st);
+#define KM_RUN(DD) return km_assign_run<DD>(X, N, C, k, bias, labels, score, st)
+    ARL_DISPATCH_WIDTH(d, KM_RUN);
+#undef KM_RUN
 }
 
 int64_t arl_kmeans_chunk_rows(void) { return kChunk; }
 
 int64_t arl_kmeans_update_workspace_bytes(int64_t N, int64_t k, int64_t d) {
-    if (N <= 0 || k <= 0 || !km_width(d)) return 0;
+    if (N <= 0 || k <= 0 || !arl_width_ok(d)) return 0;
     return (int64_t)sizeof(float) * (N / kChunk + k) * d;          // sum_c ceil(count_c / kChunk) <= N / kChunk + k
 }
 
 int arl_kmeans_update_f32(const float *X, int64_t N, int64_t d, const int32_t *order, const int32_t *seg_ptr, const int32_t *chunk_ptr, int64_t k, const float *C_prev,
                           float *C_new, void *workspace, arl_stream_t stream) {
     if (!X || !order || !seg_ptr || !chunk_ptr || !C_prev || !C_new || !workspace) return ARL_E_NULL;
-    if (!km_width(d)) return ARL_E_DIM;
+    if (!arl_width_ok(d)) return ARL_E_DIM;
     if (N <= 0 || k <= 0 || C_prev == C_new) return ARL_E_ARG;
     if (N > 0x7fffffffll / 128 || k > 0x7fffffffll / 128) return ARL_E_RANGE;
     if (((uintptr_t)X | (uintptr_t)workspace) & 15) return ARL_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     float *part = (float *)workspace;
     hipLaunchKernelGGL(km_segsum_kernel, dim3((unsigned)(N / kChunk + k)), dim3(kBlk), 0, st, X, (int)N, (int)d, order, seg_ptr, chunk_ptr, (int)k, part);
-    KM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(km_mean_kernel, dim3((unsigned)((k * d + kBlk - 1) / kBlk)), dim3(kBlk), 0, st, (const float *)part, seg_ptr, chunk_ptr, (int)k, (int)d, C_prev, C_new);
-    KM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -498,9 +456,9 @@ int arl_kmeans_sum_f64(const float *v, int64_t n, int32_t squared, double *out, 
     const long long span = (n + parts - 1) / parts;
     parts = (n + span - 1) / span;
     hipLaunchKernelGGL(km_sum_partial_kernel, dim3((unsigned)parts), dim3(kBlk), 0, st, v, (long long)n, span, (int)squared, (double *)workspace);
-    KM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(km_sum_fold_kernel, dim3(1), dim3(kBlk), 0, st, (const double *)workspace, (int)parts, out);
-    KM_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -519,7 +477,7 @@ int64_t arl_kmeanspp_workspace_bytes(int64_t N, int64_t n_trials) {
 int arl_kmeanspp_dist_f32(const float *X, int64_t N, int64_t d, const int32_t *cand_ids, int64_t n_cand, const float *closest, float *mins, double *part,
                           arl_stream_t stream) {
     if (!X || !cand_ids || !mins || !part) return ARL_E_NULL;
-    if (!km_width(d)) return ARL_E_DIM;
+    if (!arl_width_ok(d)) return ARL_E_DIM;
     if (N <= 0 || n_cand < 1 || n_cand > kPpMaxT) return ARL_E_ARG;
     if (!km_rows(N)) return ARL_E_RANGE;
     if (((uintptr_t)X & 15) || ((uintptr_t)part & 7)) return ARL_E_ARG;
@@ -538,7 +496,7 @@ int arl_kmeanspp_pick_f64(const float *mins, const double *part, int64_t N, int6
 int arl_kmeanspp_f32(const float *X, int64_t N, int64_t d, int64_t k, int64_t n_trials, int64_t first, const double *u, int32_t *indices, float *closest,
                      int32_t *cand_ids, double *cand_pot, void *workspace, arl_stream_t stream) {
     if (!X || !indices || !closest || !workspace || (k > 1 && !u)) return ARL_E_NULL;
-    if (!km_width(d)) return ARL_E_DIM;
+    if (!arl_width_ok(d)) return ARL_E_DIM;
     if (N <= 0 || k <= 0 || k > N || n_trials < 1 || n_trials > kPpMaxT || first < 0 || first >= N) return ARL_E_ARG;
     if (!km_rows(N) || !km_rows(k)) return ARL_E_RANGE;
     if ((((uintptr_t)X | (uintptr_t)workspace) & 15) || (((uintptr_t)u | (uintptr_t)cand_pot) & 7)) return ARL_E_ARG;

@@ -6,10 +6,8 @@
 //     dq[b]  = g_b ( n_b sum_i p_bi E_i - sum_{i in pos(b)} w_bi E_i )
 //     dE[i]  = sum_b g_b ( n_b p_bi - w_bi [i in pos(b)] ) q_b
 //
-// Rules kept throughout, those of arl_policyhead.hip / arl_allpairs.hip, whose tile code this file repeats with the head's terms
-// taken out:
-//   * scores and the weighted row sums run exact fp32 on v_mfma_f32_16x16x4_f32: a wave keeps 16 rows of the RESIDENT table in registers, the
-//     STREAMED table passes through LDS 64 rows at a time (double-buffered);
+// Rules kept throughout:
+//   * scores and the weighted row sums run exact fp32 on v_mfma_f32_16x16x4_f32 on the shared streamed tile (arl_stream.h);
 //   * pass 1 (rows resident, items streamed in splits): the online row max and sum of exp, merged over the splits in ascending order;
 //     pass 2 (one wave per row): lse, the sums over the row's CSR positives (their scores by the same instructions as the stream's), nll and the
 //     row's dense coefficient a_b = g_b n_b;
@@ -23,31 +21,16 @@
 #include <stdint.h>
 #include <math.h>
 #include "arlib_amd.h"
-
-#define MN_LAUNCH_CHECK()                                   \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
+#include "arl_stream.h"
 
 namespace {
 
 constexpr int kBlk = 256, kWaves = 4;
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-// two running (max, sum of exp(. - max)) states into one; symmetric in its two states bit for bit (contraction off)
-__device__ __forceinline__ void mn_combine(float &m, float &s, float m2, float s2) {
-#pragma clang fp contract(off)
-    const float M = fmaxf(m, m2);
-    const float e1 = m == M ? 1.f : expf(m - M), e2 = m2 == M ? 1.f : expf(m2 - M);
-    const float p1 = s * e1, p2 = s2 * e2;
-    s = p1 + p2;
-    m = M;
-}
+using strm::f32x4v;
 
 enum { MN_STATS = 0, MN_DQ = 1, MN_DE = 2 };
 
-// The stream of arl_policyhead.hip's ph_stream_kernel.  Xr [nR][D] resident, Xt [nT][D] streamed, split blockIdx.y takes the streamed rows
+// Xr [nR][D] resident, Xt [nT][D] streamed, split blockIdx.y takes the streamed rows
 // [y split_len, (y + 1) split_len), split_len a multiple of 64.  In MN_STATS and MN_DQ the resident rows are the batch rows (q) and the streamed rows
 // the items (E); in MN_DE the items are resident and the batch rows streamed.  stat [B][2] = (row max, 1 / row sum), coef [B] = g_b n_b.
 //   MN_STATS: part_ms [split][nR][2] = the split's (max, sum of exp(z - max))
@@ -58,23 +41,15 @@ __global__ __launch_bounds__(kBlk) void mn_stream_kernel(const float *__restrict
                                                           const float *__restrict__ stat, const float *__restrict__ coef, float *__restrict__ out,
                                                           float *__restrict__ part_ms) {
 #pragma clang fp contract(off)
-    constexpr int Q = D / 4, LD = D + 4, NT = D / 16;
+    constexpr int NT = D / 16;
     constexpr bool GRAD = MODE != MN_STATS;
-    __shared__ float tile[2][64 * LD];
+    __shared__ float tile[2][strm::kStageFloats<D>];
     __shared__ float rsv[2][MODE == MN_DE ? 64 * 3 : 1];               // MN_DE: the streamed batch rows' (max, 1 / sum, coef)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, g = lane >> 4;
     const int r0 = (blockIdx.x * kWaves + wv) * 16;
     const int t_begin = blockIdx.y * split_len, t_end = min(nT, t_begin + split_len);
-    float br[Q];
-    {
-        const int r = r0 + c;
-#pragma unroll
-        for (int i = 0; i < Q; i += 4) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < nR) v = *reinterpret_cast<const float4 *>(Xr + (size_t)r * D + Q * g + i);
-            br[i] = v.x; br[i + 1] = v.y; br[i + 2] = v.z; br[i + 3] = v.w;
-        }
-    }
+    float br[D / 4];
+    strm::load_resident<D>(Xr, r0 + c, nR, g, br);
     // the lane's batch row when the batch rows are resident
     const int brow_id = min(r0 + c, nR - 1);
     float rm = 0.f, rinv = 0.f, rco = 0.f;
@@ -89,17 +64,12 @@ __global__ __launch_bounds__(kBlk) void mn_stream_kernel(const float *__restrict
     }
     float sm = -INFINITY, ss = 0.f;                                      // MN_STATS
     const int nst = t_end > t_begin ? (t_end - t_begin + 63) / 64 : 0;
-    constexpr int PF = 64 * (D / 4) / kBlk;
-    f32x4v pre[PF];
+    // beside a stage's rows: MN_DE's statistics and coefficient of the streamed batch rows
+    strm::stage<D> stg(tid);
     float pre_v[3] = {0.f, 0.f, 0.f};
-    const int frow = tid / (D / 4), fq = (tid % (D / 4)) * 4;
-    constexpr int FSTEP = kBlk / (D / 4);
 #define MN_FETCH(ST)                                                                                                               \
     do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) {                                                                           \
-            const int t = min(t_begin + (ST) * 64 + frow + i * FSTEP, nT - 1);     /* clamped; rows past t_end are masked below */ \
-            pre[i] = *reinterpret_cast<const f32x4v *>(Xt + (size_t)t * D + fq);                                                   \
-        }                                                                                                                          \
+        stg.fetch(Xt, t_begin + (ST) * 64, nT);                                                                                    \
         if (MODE == MN_DE && tid < 64) {                                                                                           \
             const int t = min(t_begin + (ST) * 64 + tid, nT - 1);                                                                  \
             pre_v[0] = stat[2 * (size_t)t]; pre_v[1] = stat[2 * (size_t)t + 1]; pre_v[2] = coef[t];                                \
@@ -107,7 +77,7 @@ __global__ __launch_bounds__(kBlk) void mn_stream_kernel(const float *__restrict
     } while (0)
 #define MN_STASH(BUF)                                                                                                              \
     do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) *reinterpret_cast<f32x4v *>(&tile[BUF][(frow + i * FSTEP) * LD + fq]) = pre[i]; \
+        stg.stash(tile[BUF]);                                                                                                      \
         if (MODE == MN_DE && tid < 64) {                                                                                           \
             _Pragma("unroll") for (int k = 0; k < 3; ++k) rsv[BUF][tid * 3 + k] = pre_v[k];                                        \
         }                                                                                                                          \
@@ -120,16 +90,7 @@ __global__ __launch_bounds__(kBlk) void mn_stream_kernel(const float *__restrict
         const float *T = tile[buf];
 #pragma unroll
         for (int sub = 0; sub < 4; ++sub) {
-            f32x4v sc = f32x4v{0.f, 0.f, 0.f, 0.f};
-            const float *arow = T + (sub * 16 + c) * LD + Q * g;
-#pragma unroll
-            for (int i = 0; i < Q; i += 4) {
-                const float4 a = *reinterpret_cast<const float4 *>(arow + i);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, br[i], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, br[i + 1], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, br[i + 2], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, br[i + 3], sc, 0, 0, 0);
-            }
+            const f32x4v sc = strm::scores<D>(strm::a_row<D>(T, sub, c, g), br);
             const int tb = t_begin + st * 64 + sub * 16 + 4 * g;        // streamed row of register 0
             if (MODE == MN_STATS) {
                 if (tb < t_end) {
@@ -156,21 +117,17 @@ __global__ __launch_bounds__(kBlk) void mn_stream_kernel(const float *__restrict
                 const float p = expf(sc[j] - m_) * inv_;
                 pj[j] = live ? co_ * p : 0.f;
             }
+            // strm::accumulate, written out: through the helper the items-resident form at d = 32 takes four more VGPRs and loses a wave of occupancy
+            if constexpr (GRAD) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float *brow = T + (sub * 16 + 4 * g + j) * LD + c;
+                for (int j = 0; j < 4; ++j) {
+                    const float *brow = T + (sub * 16 + 4 * g + j) * strm::kLD<D> + c;
 #pragma unroll
-                for (int n = 0; n < NT; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(pj[j], brow[16 * n], o[n], 0, 0, 0);
+                    for (int n = 0; n < NT; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(pj[j], brow[16 * n], o[n], 0, 0, 0);
+                }
             }
         }
-        if (GRAD) {
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) o2[n][reg] += (double)o[n][reg];
-                o[n] = f32x4v{0.f, 0.f, 0.f, 0.f};
-            }
-        }
+        if constexpr (GRAD) strm::flush_stage<D>(o, o2);
         if (st + 1 < nst) MN_STASH(buf ^ 1);
         __syncthreads();
     }
@@ -181,20 +138,11 @@ __global__ __launch_bounds__(kBlk) void mn_stream_kernel(const float *__restrict
 #pragma unroll
         for (int off = 16; off <= 32; off <<= 1) {
             const float m2 = __shfl_xor(sm, off), s2 = __shfl_xor(ss, off);
-            mn_combine(sm, ss, m2, s2);
+            strm::merge_lse(sm, ss, m2, s2);
         }
         if (g == 0 && r0 + c < nR) { part_ms[2 * prow] = sm; part_ms[2 * prow + 1] = ss; }
     }
-    if (GRAD) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int r = r0 + 4 * g + reg;
-                if (r >= nR) continue;
-                out[((size_t)blockIdx.y * nR + r) * D + 16 * n + c] = (float)o2[n][reg];
-            }
-    }
+    if constexpr (GRAD) strm::store_partial<D>(out, blockIdx.y, nR, r0, g, c, o2);
 }
 
 // One wave per batch row: the splits' (max, sum) states merged in ascending order, lse = max + log sum, then the row's positives 16 at a time: their
@@ -212,27 +160,14 @@ __global__ __launch_bounds__(kBlk) void mn_rows_kernel(const float *__restrict__
     const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4, b = blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (b >= B) return;                                                  // wave-uniform
     float m = part_ms[2 * (size_t)b], s = part_ms[2 * (size_t)b + 1];
-    for (int k = 1; k < ns; ++k) mn_combine(m, s, part_ms[2 * ((size_t)k * B + b)], part_ms[2 * ((size_t)k * B + b) + 1]);
+    for (int k = 1; k < ns; ++k) strm::merge_lse(m, s, part_ms[2 * ((size_t)k * B + b)], part_ms[2 * ((size_t)k * B + b) + 1]);
     const float l = m + logf(s);
     const int lo = rowptr[b], hi = rowptr[b + 1];
     float br[Q];
-#pragma unroll
-    for (int i = 0; i < Q; i += 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(q + (size_t)b * D + Q * g + i);
-        br[i] = v.x; br[i + 1] = v.y; br[i + 2] = v.z; br[i + 3] = v.w;
-    }
+    strm::load_resident<D>(q, b, B, g, br);
     double n = 0.0, swz = 0.0;
     for (int e0 = lo; e0 < hi; e0 += 16) {                               // wave-uniform trip count
-        const float *arow = E + (size_t)col[min(e0 + c, hi - 1)] * D + Q * g;
-        f32x4v sc = f32x4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < Q; i += 4) {
-            const float4 a = *reinterpret_cast<const float4 *>(arow + i);
-            sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, br[i], sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, br[i + 1], sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, br[i + 2], sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, br[i + 3], sc, 0, 0, 0);
-        }
+        const f32x4v sc = strm::scores<D>(E + (size_t)col[min(e0 + c, hi - 1)] * D + Q * g, br);
         if (c == 0) {                                                    // every column holds the same 16 scores: register j of group g is entry e0 + 4 g + j
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -298,25 +233,9 @@ __global__ __launch_bounds__(kBlk) void mn_finish_dE_kernel(const float *__restr
     dE[e] = v - (float)c;
 }
 
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-// splits of the streamed table (arl_policyhead.hip's ph_splits): enough workgroups to fill the chip several times over, at least 1 024 streamed rows
-// each, whole 64-row stages
-struct mn_split { int ns, len; };
-mn_split mn_splits(int64_t n_resident, int64_t n_streamed) {
-    const int64_t blocks = (n_resident + 63) / 64;
-    int64_t s = (2048 + blocks - 1) / blocks;
-    const int64_t max_s = (n_streamed + 1023) / 1024;
-    if (s > max_s) s = max_s;
-    if (s > 256) s = 256;
-    if (s < 1) s = 1;
-    const int64_t len = ((n_streamed + s - 1) / s + 63) / 64 * 64;
-    return mn_split{(int)((n_streamed + len - 1) / len), (int)len};
-}
-
 struct mn_layout { size_t part_ms, stat, coef, part_dq, part_dE, total; };
 mn_layout mn_plan(int64_t B, int64_t I, int64_t d, bool grad) {
-    const mn_split sq = mn_splits(B, I), sb = mn_splits(I, B);
+    const strm::split sq = strm::stage_splits(B, I), sb = strm::stage_splits(I, B);
     mn_layout L;
     size_t off = 0;
     L.part_ms = off; off += up16(sizeof(float) * 2 * (size_t)sq.ns * (size_t)B);
@@ -328,41 +247,37 @@ mn_layout mn_plan(int64_t B, int64_t I, int64_t d, bool grad) {
     return L;
 }
 
-bool mn_shape_ok(int64_t B, int64_t I, int64_t d) {
-    return (d == 16 || d == 32 || d == 64 || d == 128) && B > 0 && I > 0 && B <= 0x7fffffffll / 128 && I <= 0x7fffffffll / 128;
-}
-
 template <int D>
 int mn_run(const float *q, int64_t B, const float *E, int64_t I, const int32_t *rowptr, const int32_t *col, const float *val, const int32_t *trowptr,
            const int32_t *tcol, const int32_t *tperm, const float *g, float *nll, float *lse, float *dq, float *dE, char *ws, hipStream_t st) {
     const bool grad = dq || dE;
     const mn_layout L = mn_plan(B, I, D, grad);
-    const mn_split sq = mn_splits(B, I), sb = mn_splits(I, B);
+    const strm::split sq = strm::stage_splits(B, I), sb = strm::stage_splits(I, B);
     const dim3 blk(kBlk);
     float *stat = (float *)(ws + L.stat), *coef = (float *)(ws + L.coef);
     hipLaunchKernelGGL((mn_stream_kernel<D, MN_STATS>), dim3((unsigned)((B + 63) / 64), (unsigned)sq.ns), blk, 0, st, q, (int)B, E, (int)I, sq.len, (const float *)nullptr,
                        (const float *)nullptr, (float *)nullptr, (float *)(ws + L.part_ms));
-    MN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL((mn_rows_kernel<D>), dim3((unsigned)((B + kWaves - 1) / kWaves)), blk, 0, st, (const float *)(ws + L.part_ms), (int)B, sq.ns, q, E, rowptr, col, val,
                        grad ? g : (const float *)nullptr, stat, lse, nll, coef);
-    MN_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     if (dq) {
         float *part = (float *)(ws + L.part_dq);
         hipLaunchKernelGGL((mn_stream_kernel<D, MN_DQ>), dim3((unsigned)((B + 63) / 64), (unsigned)sq.ns), blk, 0, st, q, (int)B, E, (int)I, sq.len, (const float *)stat,
                            (const float *)coef, part, (float *)nullptr);
-        MN_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
         const size_t n = (size_t)B * D;
         hipLaunchKernelGGL((mn_finish_dq_kernel<D>), dim3((unsigned)((n + kBlk - 1) / kBlk)), blk, 0, st, (const float *)part, (int)B, sq.ns, E, rowptr, col, val, g, dq);
-        MN_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
     }
     if (dE) {
         float *part = (float *)(ws + L.part_dE);
         hipLaunchKernelGGL((mn_stream_kernel<D, MN_DE>), dim3((unsigned)((I + 63) / 64), (unsigned)sb.ns), blk, 0, st, E, (int)I, q, (int)B, sb.len, (const float *)stat,
                            (const float *)coef, part, (float *)nullptr);
-        MN_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
         const size_t n = (size_t)I * D;
         hipLaunchKernelGGL((mn_finish_dE_kernel<D>), dim3((unsigned)((n + kBlk - 1) / kBlk)), blk, 0, st, (const float *)part, (int)I, sb.ns, q, trowptr, tcol, tperm, val, g, dE);
-        MN_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
     }
     return ARL_OK;
 }
@@ -372,7 +287,7 @@ int mn_run(const float *q, int64_t B, const float *E, int64_t I, const int32_t *
 extern "C" {
 
 int64_t arl_multinomial_softmax_workspace_bytes(int64_t B, int64_t I, int64_t d, int32_t want_grad) {
-    if (!mn_shape_ok(B, I, d)) return 0;
+    if (!strm::shape_ok(B, I, d)) return 0;
     return (int64_t)mn_plan(B, I, d, want_grad != 0).total;
 }
 
@@ -389,10 +304,7 @@ int arl_multinomial_softmax_f32(const float *q, int64_t B, const float *E, int64
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
 #define MN_RUN(DD) return mn_run<DD>(q, B, E, I, rowptr, col, val, trowptr, tcol, tperm, g, nll, lse, dq, dE, ws, st)
-    if (d == 16) MN_RUN(16);
-    if (d == 32) MN_RUN(32);
-    if (d == 64) MN_RUN(64);
-    MN_RUN(128);
+    ARL_DISPATCH_WIDTH(d, MN_RUN);
 #undef MN_RUN
 }
 

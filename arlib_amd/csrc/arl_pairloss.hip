@@ -4,10 +4,9 @@
 // distances (torch.pdist); here none is stored.  Rules kept throughout:
 //   * dist^2_ij = max(q_i + q_j - 2 <y_i, y_j>, 0) with q_r = |y_r|^2 kept per row: rows are NOT assumed to have unit length (F.normalize leaves a
 //     zero row at zero and scales a row of norm < 1e-12 by 1e12);
-//   * products run exact fp32 on v_mfma_f32_16x16x4_f32 in the layout of the all-rows InfoNCE kernel: a wave keeps 16 RESIDENT rows in registers,
-//     the STREAMED rows and their q pass through LDS 64 rows at a time (double-buffered), e = exp(-t dist^2) of the score tile is already in
-//     A-operand layout for the second product G_i = sum_j e_ij y_j, which runs on v_mfma_f64_16x16x4_f64 (same operand layout; result register reg of
-//     lane (c, g) is row g + 4 reg, not 4 g + reg);
+//   * products run exact fp32 on v_mfma_f32_16x16x4_f32 on the shared streamed tile (arl_stream.h), the streamed rows' q beside each stage;
+//     e = exp(-t dist^2) of the score tile is already in A-operand layout for the second product G_i = sum_j e_ij y_j, which runs here on
+//     v_mfma_f64_16x16x4_f64 (same operand layout; result register reg of lane (c, g) is row g + 4 reg, not 4 g + reg);
 //   * the diagonal is masked (e_ii never enters a sum), rows past a split's end likewise; the plain both-orders sweep, no triangle skipped;
 //   * every sum has a fixed order (no float atomics): a lane's four scores, the stage's four tiles, the four lane groups by two butterflies, the
 //     splits of the streamed side in split order, S = sum_i rowsum_i in double over fixed spans (arl_kmeans_sum_f64);
@@ -23,18 +22,13 @@
 #include <stdint.h>
 #include <math.h>
 #include "arlib_amd.h"
-
-#define PL_LAUNCH_CHECK()                                   \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
+#include "arl_stream.h"
 
 namespace {
 
 constexpr int kBlk = 256, kWaves = 4;
 constexpr int kSplitRows = 256;              // a split of the streamed side has at least this many rows
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+using strm::f32x4v;
 typedef double f64x4v __attribute__((ext_vector_type(4)));
 
 // q[r] = |Y[r]|^2, one thread per row, components in order
@@ -55,47 +49,32 @@ __global__ __launch_bounds__(kBlk) void unif_q_kernel(const float *__restrict__ 
 template <int D, bool GRAD>
 __global__ __launch_bounds__(kBlk) void unif_pairs_kernel(const float *__restrict__ Y, const float *__restrict__ q, int n, int split_len, float neg_t,
                                                            float *__restrict__ part, float *__restrict__ sums) {
-    constexpr int Q = D / 4, LD = D + 4, NT = D / 16;
-    __shared__ __attribute__((aligned(16))) float tile[2][64 * LD];
+    constexpr int LD = strm::kLD<D>, NT = D / 16;
+    __shared__ __attribute__((aligned(16))) float tile[2][strm::kStageFloats<D>];
     __shared__ __attribute__((aligned(16))) float tq[2][64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, g = lane >> 4;
     const int r0 = (blockIdx.x * kWaves + wv) * 16;
     const int t_begin = blockIdx.y * split_len, t_end = min(n, t_begin + split_len);
-    float br[Q];
-    {
-        const int r = r0 + c;
-#pragma unroll
-        for (int i = 0; i < Q; i += 4) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < n) v = *reinterpret_cast<const float4 *>(Y + (size_t)r * D + Q * g + i);
-            br[i] = v.x; br[i + 1] = v.y; br[i + 2] = v.z; br[i + 3] = v.w;
-        }
-    }
+    float br[D / 4];
+    strm::load_resident<D>(Y, r0 + c, n, g, br);
     const float q_r = r0 + c < n ? q[r0 + c] : 0.f;
     f64x4v od[NT];                           // G's tile and the row sums, in double
 #pragma unroll
     for (int m = 0; m < NT; ++m) od[m] = f64x4v{0.0, 0.0, 0.0, 0.0};
     double sumd = 0.0;
     const int nst = t_end > t_begin ? (t_end - t_begin + 63) / 64 : 0;
-    // a stage is 64 x D floats = 16 D float4s over 256 threads; the NEXT stage is fetched into registers before the current one is consumed
-    // and goes to the other LDS buffer afterwards (macros, not lambdas: an array captured by reference stays in scratch memory)
-    constexpr int PF = 64 * (D / 4) / kBlk;
-    f32x4v pre[PF];
+    // beside a stage's rows: their q, fetched and stashed with them
+    strm::stage<D> stg(tid);
     float pre_q = 0.f;
-    const int frow = tid / (D / 4), fq = (tid % (D / 4)) * 4;
-    constexpr int FSTEP = kBlk / (D / 4);
-#define PL_FETCH(ST)                                                                                                               \
-    do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) {                                                                           \
-            const int t = min(t_begin + (ST) * 64 + frow + i * FSTEP, n - 1);      /* clamped; rows past t_end are masked below */  \
-            pre[i] = *reinterpret_cast<const f32x4v *>(Y + (size_t)t * D + fq);                                                    \
-        }                                                                                                                          \
-        if (tid < 64) pre_q = q[min(t_begin + (ST) * 64 + tid, n - 1)];                                                            \
+#define PL_FETCH(ST)                                                    \
+    do {                                                                \
+        stg.fetch(Y, t_begin + (ST) * 64, n);                           \
+        if (tid < 64) pre_q = q[min(t_begin + (ST) * 64 + tid, n - 1)]; \
     } while (0)
-#define PL_STASH(BUF)                                                                                                              \
-    do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) *reinterpret_cast<f32x4v *>(&tile[BUF][(frow + i * FSTEP) * LD + fq]) = pre[i]; \
-        if (tid < 64) tq[BUF][tid] = pre_q;                                                                                        \
+#define PL_STASH(BUF)                       \
+    do {                                    \
+        stg.stash(tile[BUF]);               \
+        if (tid < 64) tq[BUF][tid] = pre_q; \
     } while (0)
     if (nst > 0) { PL_FETCH(0); PL_STASH(0); }
     __syncthreads();
@@ -103,13 +82,14 @@ __global__ __launch_bounds__(kBlk) void unif_pairs_kernel(const float *__restric
         const int buf = st & 1;
         if (st + 1 < nst) PL_FETCH(st + 1);
         const float *T = tile[buf];
-        // the stage's four 16-row tiles on four independent accumulators (the 16x16x4 form needs >= 2 to reach its issue rate)
+        // the stage's four 16-row tiles on four independent accumulators: strm::scores4, written out (through the helper the gradient form at
+        // d = 64 moves 14 registers to the AGPR side and loses a wave of occupancy)
         f32x4v sc[4];
 #pragma unroll
         for (int sub = 0; sub < 4; ++sub) sc[sub] = f32x4v{0.f, 0.f, 0.f, 0.f};
-        const float *arow = T + c * LD + Q * g;
+        const float *arow = strm::a_row<D>(T, 0, c, g);
 #pragma unroll
-        for (int i = 0; i < Q; i += 4) {
+        for (int i = 0; i < D / 4; i += 4) {
             float4 a[4];
 #pragma unroll
             for (int sub = 0; sub < 4; ++sub) a[sub] = *reinterpret_cast<const float4 *>(arow + sub * 16 * LD + i);
@@ -245,8 +225,6 @@ __global__ __launch_bounds__(kBlk) void align_mean_kernel(const float *__restric
     if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)n);
 }
 
-bool pl_width(int64_t d) { return d == 16 || d == 32 || d == 64 || d == 128; }
-
 bool pl_rows(int64_t n) { return n >= 2 && n <= 0x7fffffffll / 128; }
 
 // splits of the streamed side: enough workgroups to fill the chip several times over, at least kSplitRows streamed rows each
@@ -292,7 +270,7 @@ int unif_pairs_run(const UnifWs &w, int64_t n, int ns, float t, bool grad, hipSt
     const dim3 grid((unsigned)((n + 63) / 64), (unsigned)ns);
     if (grad) hipLaunchKernelGGL((unif_pairs_kernel<D, true>), grid, dim3(kBlk), 0, st, (const float *)w.Y, (const float *)w.q, (int)n, split_len, -t, w.part, w.sums);
     else hipLaunchKernelGGL((unif_pairs_kernel<D, false>), grid, dim3(kBlk), 0, st, (const float *)w.Y, (const float *)w.q, (int)n, split_len, -t, w.part, w.sums);
-    PL_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -303,13 +281,13 @@ extern "C" {
 int64_t arl_uniformity_splits(int64_t n) { return pl_rows(n) ? unif_splits(n) : 0; }
 
 int64_t arl_uniformity_workspace_bytes(int64_t n, int64_t d) {
-    if (!pl_rows(n) || !pl_width(d)) return 0;
+    if (!pl_rows(n) || !arl_width_ok(d)) return 0;
     return unif_ws(nullptr, n, d, unif_splits(n)).bytes;
 }
 
 int arl_uniformity_fwd_bwd_f32(const float *X, int64_t n, int64_t d, float t, float upstream, float *loss, float *dX, void *workspace, arl_stream_t stream) {
     if (!X || !loss || !workspace) return ARL_E_NULL;
-    if (!pl_width(d)) return ARL_E_DIM;
+    if (!arl_width_ok(d)) return ARL_E_DIM;
     if (n < 2 || !(t > 0.f)) return ARL_E_ARG;
     if (!pl_rows(n)) return ARL_E_RANGE;
     if (((uintptr_t)X | (uintptr_t)dX | (uintptr_t)workspace) & 15) return ARL_E_ARG;
@@ -320,20 +298,20 @@ int arl_uniformity_fwd_bwd_f32(const float *X, int64_t n, int64_t d, float t, fl
     int rc = arl_normalize_rows_f32(X, n, d, w.Y, w.nrm, stream);
     if (rc != ARL_OK) return rc;
     hipLaunchKernelGGL(unif_q_kernel, dim3((unsigned)((n + kBlk - 1) / kBlk)), dim3(kBlk), 0, st, (const float *)w.Y, (int)n, (int)d, w.q);
-    PL_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     if (d == 16) rc = unif_pairs_run<16>(w, n, ns, t, grad, st);
     else if (d == 32) rc = unif_pairs_run<32>(w, n, ns, t, grad, st);
     else if (d == 64) rc = unif_pairs_run<64>(w, n, ns, t, grad, st);
     else rc = unif_pairs_run<128>(w, n, ns, t, grad, st);
     if (rc != ARL_OK) return rc;
     hipLaunchKernelGGL(unif_rowsum_kernel, dim3((unsigned)((n + kBlk - 1) / kBlk)), dim3(kBlk), 0, st, (const float *)w.sums, ns, (int)n, w.rowsum);
-    PL_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     rc = arl_kmeans_sum_f64(w.rowsum, n, 0, w.S, w.sum_ws, stream);
     if (rc != ARL_OK) return rc;
     const long long n4 = (long long)n * (d / 4), blocks = (n4 + kBlk - 1) / kBlk;
     hipLaunchKernelGGL(unif_finish_kernel, dim3(grad ? (unsigned)(blocks < 16384 ? blocks : 16384) : 1u), dim3(kBlk), 0, st, (const double *)w.S, t, (int)n, (int)(d / 4),
                        grad ? (const float4 *)w.part : (const float4 *)nullptr, ns, loss, (float4 *)w.dYn);
-    PL_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     if (!grad) return ARL_OK;
     return arl_normalize_rows_bwd_f32(w.Y, w.nrm, w.dYn, n, d, upstream, nullptr, dX, stream);
 }
@@ -350,9 +328,9 @@ int arl_alignment_fwd_bwd_f32(const float *X, const float *Y, int64_t n, int64_t
     const long long blocks = (n + kWaves - 1) / kWaves;
     hipLaunchKernelGGL(align_rows_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(kBlk), 0, st, X, Y, (long long)n, (int)d, alpha,
                        (float)((double)upstream / (double)n), terms, dX, dY);
-    PL_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(align_mean_kernel, dim3(1), dim3(kBlk), 0, st, (const float *)terms, (long long)n, loss);
-    PL_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 

@@ -5,9 +5,8 @@
 //     logp[b] = sum_i (a p - sp),     ent[b] = sum_i (sp - p sg),
 //     c_i = gl (a_i - sg_i) - ge p_i sg_i (1 - sg_i),     t_b = sum_j p_j c_j,     dz_i = p_i (c_i - t_b),     dq = dz E,     dE = dz^T q.
 //
-// Rules kept throughout, those of arl_allpairs.hip / arl_colsoftmax.hip:
-//   * scores and the weighted row sums run exact fp32 on v_mfma_f32_16x16x4_f32: a wave keeps 16 rows of the RESIDENT table in registers, the
-//     STREAMED table passes through LDS 64 rows at a time (double-buffered);
+// Rules kept throughout:
+//   * scores and the weighted row sums run exact fp32 on v_mfma_f32_16x16x4_f32 on the shared streamed tile (arl_stream.h);
 //   * pass 1 (rows resident, items streamed in splits): the online row max and sum of exp, merged over the splits in ascending order;
 //     pass 2: the row sums logp, ent, t (or, sampling: the action bits, logp and the count);   pass 3: dq;   pass 4 (items resident, rows streamed in
 //     splits): dE.  Item splits are whole 64-item stages, so one lane writes each action word; B = 1 is spread over the chip by the splits, and
@@ -19,36 +18,18 @@
 #include <stdint.h>
 #include <math.h>
 #include "arlib_amd.h"
-
-#define PH_LAUNCH_CHECK()                                   \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
+#include "arl_stream.h"
 
 namespace {
 
 constexpr int kBlk = 256, kWaves = 4;
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+using strm::f32x4v;
 
-__device__ __forceinline__ uint64_t ph_smix(uint64_t x) {      // the splitmix64 finaliser of arl_profilegen.hip / arl_gan.hip
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-uint64_t ph_host_key(uint64_t seed, uint64_t call) {            // arl_gan_hash_key's hash of (seed, call)
-    uint64_t x = seed ^ (call * 0x9E3779B97F4A7C15ull);
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 // arl_profilegen.hip's row key with round 0: the draw at (row, i) is a function of (seed, call, row, i) only
-__device__ __forceinline__ uint64_t ph_rowkey(uint64_t key, int row) { return ph_smix(key ^ (uint64_t)(uint32_t)row); }
+__device__ __forceinline__ uint64_t ph_rowkey(uint64_t key, int row) { return arl_splitmix64(key ^ (uint64_t)(uint32_t)row); }
 // u = n 2^-24 for the 24-bit draw n: exact in fp32, in [0, 1)
 __device__ __forceinline__ float ph_uniform(uint64_t rowkey, int i) {
-    return (float)(uint32_t)(ph_smix(rowkey ^ (uint64_t)(uint32_t)i) >> 40) * (1.0f / 16777216.0f);
+    return (float)(uint32_t)(arl_splitmix64(rowkey ^ (uint64_t)(uint32_t)i) >> 40) * (1.0f / 16777216.0f);
 }
 
 // p = exp(z - m) / s, sg = sigmoid(p), sp = softplus(p) = p + log1p(exp(-p)) for p in [0, 1].  Contraction is off so that every pass gets the same bits.
@@ -60,20 +41,10 @@ __device__ __forceinline__ void ph_terms(float z, float m, float inv, float &p, 
     sp = p + log1pf(en);
 }
 
-// two running (max, sum of exp(. - max)) states into one; symmetric in its two states bit for bit (contraction off)
-__device__ __forceinline__ void ph_combine(float &m, float &s, float m2, float s2) {
-#pragma clang fp contract(off)
-    const float M = fmaxf(m, m2);
-    const float e1 = m == M ? 1.f : expf(m - M), e2 = m2 == M ? 1.f : expf(m2 - M);
-    const float p1 = s * e1, p2 = s2 * e2;
-    s = p1 + p2;
-    m = M;
-}
-
 enum { PH_STATS = 0, PH_SUMS = 1, PH_SAMPLE = 2, PH_DQ = 3, PH_DE = 4 };
 enum { PH_U_TENSOR = 0, PH_U_HASH = 1, PH_U_MODE = 2 };
 
-// The stream of arl_allpairs.hip's bap_stream_kernel.  Xr [nR][D] resident, Xt [nT][D] streamed, split blockIdx.y takes the streamed rows
+// Xr [nR][D] resident, Xt [nT][D] streamed, split blockIdx.y takes the streamed rows
 // [y split_len, (y + 1) split_len).  In every mode but PH_DE the resident rows are the batch rows (q) and the streamed rows the items (E), and split_len
 // is a multiple of 64; in PH_DE the items are resident and the batch rows streamed.  stat [B][2] = (row max, 1 / row sum).
 //   PH_STATS : part_ms [split][nR][2] = the split's (max, sum of exp(z - max))
@@ -88,24 +59,16 @@ __global__ __launch_bounds__(kBlk) void ph_stream_kernel(const float *__restrict
                                                           const float *__restrict__ u, uint64_t key, int row0, int usrc, float *__restrict__ out,
                                                           float *__restrict__ part_ms, double *__restrict__ part_sum) {
 #pragma clang fp contract(off)
-    constexpr int Q = D / 4, LD = D + 4, NT = D / 16;
+    constexpr int NT = D / 16;
     constexpr bool GRAD = MODE == PH_DQ || MODE == PH_DE, ROWS = MODE != PH_DE, BITS = MODE == PH_SUMS || MODE == PH_DQ;
-    __shared__ float tile[2][64 * LD];
+    __shared__ float tile[2][strm::kStageFloats<D>];
     __shared__ float rsv[2][MODE == PH_DE ? 64 * 5 : 1];               // PH_DE: the streamed batch rows' (max, 1 / sum, gl, ge, t)
     __shared__ uint32_t rsw[2][MODE == PH_DE ? 64 * 2 : 1];            // PH_DE: their two action words over this workgroup's 64 items
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = lane & 15, g = lane >> 4;
     const int r0 = (blockIdx.x * kWaves + wv) * 16;
     const int t_begin = blockIdx.y * split_len, t_end = min(nT, t_begin + split_len);
-    float br[Q];
-    {
-        const int r = r0 + c;
-#pragma unroll
-        for (int i = 0; i < Q; i += 4) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < nR) v = *reinterpret_cast<const float4 *>(Xr + (size_t)r * D + Q * g + i);
-            br[i] = v.x; br[i + 1] = v.y; br[i + 2] = v.z; br[i + 3] = v.w;
-        }
-    }
+    float br[D / 4];
+    strm::load_resident<D>(Xr, r0 + c, nR, g, br);
     // the lane's batch row when the batch rows are resident
     const int brow_id = min(r0 + c, nR - 1);
     float rm = 0.f, rinv = 0.f, rgl = 0.f, rge = 0.f, rt = 0.f;
@@ -129,20 +92,15 @@ __global__ __launch_bounds__(kBlk) void ph_stream_kernel(const float *__restrict
     double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;                           // PH_SUMS / PH_SAMPLE
     int cnt = 0;
     const int nst = t_end > t_begin ? (t_end - t_begin + 63) / 64 : 0;
-    constexpr int PF = 64 * (D / 4) / kBlk;
-    f32x4v pre[PF];
+    // beside a stage's rows: PH_DE's statistics and action words of the streamed batch rows, BITS' action words of the lane's own row
+    strm::stage<D> stg(tid);
     float pre_v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     uint32_t pre_w[2] = {0u, 0u};
     uint32_t aw_next[2] = {0u, 0u}, aw[2] = {0u, 0u};                    // BITS: the lane's batch row's two action words of a stage
-    const int frow = tid / (D / 4), fq = (tid % (D / 4)) * 4;
-    constexpr int FSTEP = kBlk / (D / 4);
     const int W0 = 2 * blockIdx.x;                                       // PH_DE: the first action word of this workgroup's items
 #define PH_FETCH(ST)                                                                                                               \
     do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) {                                                                           \
-            const int t = min(t_begin + (ST) * 64 + frow + i * FSTEP, nT - 1);     /* clamped; rows past t_end are masked below */ \
-            pre[i] = *reinterpret_cast<const f32x4v *>(Xt + (size_t)t * D + fq);                                                   \
-        }                                                                                                                          \
+        stg.fetch(Xt, t_begin + (ST) * 64, nT);                                                                                    \
         if (MODE == PH_DE && tid < 64) {                                                                                           \
             const int t = min(t_begin + (ST) * 64 + tid, nT - 1);                                                                  \
             pre_v[0] = stat[2 * (size_t)t]; pre_v[1] = stat[2 * (size_t)t + 1]; pre_v[2] = gl[t]; pre_v[3] = ge[t]; pre_v[4] = tt[t]; \
@@ -157,7 +115,7 @@ __global__ __launch_bounds__(kBlk) void ph_stream_kernel(const float *__restrict
     } while (0)
 #define PH_STASH(BUF)                                                                                                              \
     do {                                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < PF; ++i) *reinterpret_cast<f32x4v *>(&tile[BUF][(frow + i * FSTEP) * LD + fq]) = pre[i]; \
+        stg.stash(tile[BUF]);                                                                                                      \
         if (MODE == PH_DE && tid < 64) {                                                                                           \
             _Pragma("unroll") for (int k = 0; k < 5; ++k) rsv[BUF][tid * 5 + k] = pre_v[k];                                        \
             rsw[BUF][tid * 2] = pre_w[0]; rsw[BUF][tid * 2 + 1] = pre_w[1];                                                        \
@@ -174,16 +132,7 @@ __global__ __launch_bounds__(kBlk) void ph_stream_kernel(const float *__restrict
         uint32_t wbits[2] = {0u, 0u};
 #pragma unroll
         for (int sub = 0; sub < 4; ++sub) {
-            f32x4v sc = f32x4v{0.f, 0.f, 0.f, 0.f};
-            const float *arow = T + (sub * 16 + c) * LD + Q * g;
-#pragma unroll
-            for (int i = 0; i < Q; i += 4) {
-                const float4 a = *reinterpret_cast<const float4 *>(arow + i);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, br[i], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, br[i + 1], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, br[i + 2], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, br[i + 3], sc, 0, 0, 0);
-            }
+            const f32x4v sc = strm::scores<D>(strm::a_row<D>(T, sub, c, g), br);
             const int tb = t_begin + st * 64 + sub * 16 + 4 * g;        // streamed row of register 0
             if (MODE == PH_STATS) {
                 if (tb < t_end) {
@@ -238,14 +187,7 @@ __global__ __launch_bounds__(kBlk) void ph_stream_kernel(const float *__restrict
             }
             if (MODE == PH_SUMS || MODE == PH_SAMPLE) st0 += (f0[0] + f0[1]) + (f0[2] + f0[3]);
             if (MODE == PH_SUMS) { st1 += (f1[0] + f1[1]) + (f1[2] + f1[3]); st2 += (f2[0] + f2[1]) + (f2[2] + f2[3]); }
-            if (GRAD) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float *brow = T + (sub * 16 + 4 * g + j) * LD + c;
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(pj[j], brow[16 * n], o[n], 0, 0, 0);
-                }
-            }
+            if constexpr (GRAD) strm::accumulate<D>(T, sub, c, g, pj, o);
         }
         if (MODE == PH_SUMS || MODE == PH_SAMPLE) acc0 += (double)st0;   // 16 scores in fp32, the stages in double
         if (MODE == PH_SUMS) { acc1 += (double)st1; acc2 += (double)st2; }
@@ -260,14 +202,7 @@ __global__ __launch_bounds__(kBlk) void ph_stream_kernel(const float *__restrict
                 if (g == 0 && r0 + c < nR && w < W) act_out[(size_t)(r0 + c) * W + w] = v;
             }
         }
-        if (GRAD) {
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) o2[n][reg] += (double)o[n][reg];
-                o[n] = f32x4v{0.f, 0.f, 0.f, 0.f};
-            }
-        }
+        if constexpr (GRAD) strm::flush_stage<D>(o, o2);
         if (st + 1 < nst) PH_STASH(buf ^ 1);
         __syncthreads();
     }
@@ -278,7 +213,7 @@ __global__ __launch_bounds__(kBlk) void ph_stream_kernel(const float *__restrict
 #pragma unroll
         for (int off = 16; off <= 32; off <<= 1) {
             const float m2 = __shfl_xor(sm, off), s2 = __shfl_xor(ss, off);
-            ph_combine(sm, ss, m2, s2);
+            strm::merge_lse(sm, ss, m2, s2);
         }
         if (g == 0 && r0 + c < nR) { part_ms[2 * prow] = sm; part_ms[2 * prow + 1] = ss; }
     }
@@ -290,16 +225,7 @@ __global__ __launch_bounds__(kBlk) void ph_stream_kernel(const float *__restrict
         }
         if (g == 0 && r0 + c < nR) { part_sum[3 * prow] = acc0; part_sum[3 * prow + 1] = acc1; part_sum[3 * prow + 2] = acc2; }
     }
-    if (GRAD) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int r = r0 + 4 * g + reg;
-                if (r >= nR) continue;
-                out[((size_t)blockIdx.y * nR + r) * D + 16 * n + c] = (float)o2[n][reg];
-            }
-    }
+    if constexpr (GRAD) strm::store_partial<D>(out, blockIdx.y, nR, r0, g, c, o2);
 }
 
 // stat [B][2] = (max, 1 / sum) from the splits' states, ascending
@@ -308,7 +234,7 @@ __global__ __launch_bounds__(kBlk) void ph_merge_stats_kernel(const float *__res
     const int b = blockIdx.x * kBlk + threadIdx.x;
     if (b >= B) return;
     float m = part_ms[2 * (size_t)b], s = part_ms[2 * (size_t)b + 1];
-    for (int k = 1; k < ns; ++k) ph_combine(m, s, part_ms[2 * ((size_t)k * B + b)], part_ms[2 * ((size_t)k * B + b) + 1]);
+    for (int k = 1; k < ns; ++k) strm::merge_lse(m, s, part_ms[2 * ((size_t)k * B + b)], part_ms[2 * ((size_t)k * B + b) + 1]);
     stat[2 * (size_t)b] = m;
     stat[2 * (size_t)b + 1] = 1.0f / s;
 }
@@ -344,20 +270,8 @@ __global__ __launch_bounds__(kBlk) void ph_uniforms_kernel(uint64_t key, int row
     out[(size_t)b * I + i] = ph_uniform(ph_rowkey(key, row0 + b), i);
 }
 
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-// splits of the streamed table: enough workgroups to fill the chip several times over, at least 1 024 streamed rows each, whole 64-row stages
-struct ph_split { int ns, len; };
-ph_split ph_splits(int64_t n_resident, int64_t n_streamed) {
-    const int64_t blocks = (n_resident + 63) / 64;
-    int64_t s = (2048 + blocks - 1) / blocks;
-    const int64_t max_s = (n_streamed + 1023) / 1024;
-    if (s > max_s) s = max_s;
-    if (s > 256) s = 256;
-    if (s < 1) s = 1;
-    const int64_t len = ((n_streamed + s - 1) / s + 63) / 64 * 64;
-    return ph_split{(int)((n_streamed + len - 1) / len), (int)len};
-}
+// the dq and dE streams split by strm::stage_splits
+using ph_split = strm::split;
 
 // splits of the items for the row statistics, the row sums and the sampling pass: a function of I alone (at least 1 024 items each, whole stages), so
 // a row's statistics, and with them its sampled bits, do not depend on how many rows the call has.  A one-row call is a chain of stages per
@@ -371,7 +285,7 @@ ph_split ph_item_splits(int64_t I) {
 
 struct ph_layout { size_t part_ms, stat, part_sum, tt, part_dq, part_dE, total; };
 ph_layout ph_plan(int64_t B, int64_t I, int64_t d, bool grad) {
-    const ph_split si = ph_item_splits(I), sq = ph_splits(B, I), sb = ph_splits(I, B);
+    const ph_split si = ph_item_splits(I), sq = strm::stage_splits(B, I), sb = strm::stage_splits(I, B);
     ph_layout L;
     size_t off = 0;
     L.part_ms = off; off += up16(sizeof(float) * 2 * (size_t)si.ns * (size_t)B);
@@ -384,19 +298,15 @@ ph_layout ph_plan(int64_t B, int64_t I, int64_t d, bool grad) {
     return L;
 }
 
-bool ph_shape_ok(int64_t B, int64_t I, int64_t d) {
-    return (d == 16 || d == 32 || d == 64 || d == 128) && B > 0 && I > 0 && B <= 0x7fffffffll / 128 && I <= 0x7fffffffll / 128;
-}
-
 template <int D>
 int ph_stats(const float *q, int64_t B, const float *E, int64_t I, char *ws, const ph_layout &L, const ph_split &si, hipStream_t st) {
     const dim3 blk(kBlk), grid((unsigned)((B + 63) / 64), (unsigned)si.ns), rows((unsigned)((B + kBlk - 1) / kBlk));
     hipLaunchKernelGGL((ph_stream_kernel<D, PH_STATS>), grid, blk, 0, st, q, (int)B, E, (int)I, si.len, (const float *)nullptr, (const float *)nullptr,
                        (const float *)nullptr, (const float *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0, (const float *)nullptr, 0ull, 0, 0,
                        (float *)nullptr, (float *)(ws + L.part_ms), (double *)nullptr);
-    PH_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(ph_merge_stats_kernel, rows, blk, 0, st, (const float *)(ws + L.part_ms), (int)B, si.ns, (float *)(ws + L.stat));
-    PH_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -405,7 +315,7 @@ int ph_eval(const float *q, int64_t B, const float *E, int64_t I, const uint32_t
             float *dE, char *ws, hipStream_t st) {
     const bool grad = dq || dE;
     const ph_layout L = ph_plan(B, I, D, grad);
-    const ph_split si = ph_item_splits(I), sq = ph_splits(B, I), sb = ph_splits(I, B);
+    const ph_split si = ph_item_splits(I), sq = strm::stage_splits(B, I), sb = strm::stage_splits(I, B);
     const int W = (int)((I + 31) / 32);
     const dim3 blk(kBlk), grid((unsigned)((B + 63) / 64), (unsigned)si.ns), rows((unsigned)((B + kBlk - 1) / kBlk));
     const float *stat = (const float *)(ws + L.stat);
@@ -414,29 +324,29 @@ int ph_eval(const float *q, int64_t B, const float *E, int64_t I, const uint32_t
     if (rc != ARL_OK) return rc;
     hipLaunchKernelGGL((ph_stream_kernel<D, PH_SUMS>), grid, blk, 0, st, q, (int)B, E, (int)I, si.len, stat, gl, ge, (const float *)nullptr, act, (uint32_t *)nullptr, W,
                        (const float *)nullptr, 0ull, 0, 0, (float *)nullptr, (float *)nullptr, (double *)(ws + L.part_sum));
-    PH_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(ph_finish_sums_kernel, rows, blk, 0, st, (const double *)(ws + L.part_sum), (int)B, si.ns, logp, ent, (int32_t *)nullptr, tt);
-    PH_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     if (dq) {
         float *dst = sq.ns > 1 ? (float *)(ws + L.part_dq) : dq;
         hipLaunchKernelGGL((ph_stream_kernel<D, PH_DQ>), dim3((unsigned)((B + 63) / 64), (unsigned)sq.ns), blk, 0, st, q, (int)B, E, (int)I, sq.len, stat, gl, ge, (const float *)tt, act, (uint32_t *)nullptr, W,
                            (const float *)nullptr, 0ull, 0, 0, dst, (float *)nullptr, (double *)nullptr);
-        PH_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
         if (sq.ns > 1) {
             const size_t n = (size_t)B * D;
             hipLaunchKernelGGL(ph_fold_kernel, dim3((unsigned)((n + kBlk - 1) / kBlk)), blk, 0, st, (const float *)dst, n, sq.ns, dq);
-            PH_LAUNCH_CHECK();
+            ARL_LAUNCH_CHECK();
         }
     }
     if (dE) {
         float *dst = sb.ns > 1 ? (float *)(ws + L.part_dE) : dE;
         hipLaunchKernelGGL((ph_stream_kernel<D, PH_DE>), dim3((unsigned)((I + 63) / 64), (unsigned)sb.ns), blk, 0, st, E, (int)I, q, (int)B, sb.len, stat, gl, ge,
                            (const float *)tt, act, (uint32_t *)nullptr, W, (const float *)nullptr, 0ull, 0, 0, dst, (float *)nullptr, (double *)nullptr);
-        PH_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
         if (sb.ns > 1) {
             const size_t n = (size_t)I * D;
             hipLaunchKernelGGL(ph_fold_kernel, dim3((unsigned)((n + kBlk - 1) / kBlk)), blk, 0, st, (const float *)dst, n, sb.ns, dE);
-            PH_LAUNCH_CHECK();
+            ARL_LAUNCH_CHECK();
         }
     }
     return ARL_OK;
@@ -454,9 +364,9 @@ int ph_sample(const float *q, int64_t B, const float *E, int64_t I, const float 
     hipLaunchKernelGGL((ph_stream_kernel<D, PH_SAMPLE>), grid, blk, 0, st, q, (int)B, E, (int)I, si.len, (const float *)(ws + L.stat), (const float *)nullptr,
                        (const float *)nullptr, (const float *)nullptr, (const uint32_t *)nullptr, act, W, u, key, (int)row0, usrc, (float *)nullptr, (float *)nullptr,
                        (double *)(ws + L.part_sum));
-    PH_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(ph_finish_sums_kernel, rows, blk, 0, st, (const double *)(ws + L.part_sum), (int)B, si.ns, logp, (float *)nullptr, count, (float *)nullptr);
-    PH_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -465,7 +375,7 @@ int ph_sample(const float *q, int64_t B, const float *E, int64_t I, const float 
 extern "C" {
 
 int64_t arl_bernoulli_softmax_workspace_bytes(int64_t B, int64_t I, int64_t d, int32_t want_grad) {
-    if (!ph_shape_ok(B, I, d)) return 0;
+    if (!strm::shape_ok(B, I, d)) return 0;
     return (int64_t)ph_plan(B, I, d, want_grad != 0).total;
 }
 
@@ -481,10 +391,7 @@ int arl_bernoulli_softmax_eval_f32(const float *q, int64_t B, const float *E, in
     char *ws = (char *)workspace;
     const uint32_t *act = (const uint32_t *)actions;
 #define PH_RUN(DD) return ph_eval<DD>(q, B, E, I, act, gl, ge, logp, ent, dq, dE, ws, st)
-    if (d == 16) PH_RUN(16);
-    if (d == 32) PH_RUN(32);
-    if (d == 64) PH_RUN(64);
-    PH_RUN(128);
+    ARL_DISPATCH_WIDTH(d, PH_RUN);
 #undef PH_RUN
 }
 
@@ -498,12 +405,9 @@ int arl_bernoulli_softmax_sample_f32(const float *q, int64_t B, const float *E, 
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
     const int usrc = deterministic ? PH_U_MODE : (u ? PH_U_TENSOR : PH_U_HASH);
-    const uint64_t key = ph_host_key(seed, call);
+    const uint64_t key = arl_gan_hash_key(seed, call);
 #define PH_RUN(DD) return ph_sample<DD>(q, B, E, I, u, key, row0, usrc, (uint32_t *)actions, logp, count, ws, st)
-    if (d == 16) PH_RUN(16);
-    if (d == 32) PH_RUN(32);
-    if (d == 64) PH_RUN(64);
-    PH_RUN(128);
+    ARL_DISPATCH_WIDTH(d, PH_RUN);
 #undef PH_RUN
 }
 
@@ -512,8 +416,8 @@ int arl_bernoulli_uniforms_f32(uint64_t seed, uint64_t call, int64_t row0, int64
     if (B <= 0 || I <= 0 || row0 < 0) return ARL_E_ARG;
     const int64_t ntiles = (I + kBlk - 1) / kBlk;
     if (I > 0x7fffffffll - kBlk || row0 + B > 0x7fffffffll || B * ntiles > 0x7fffffffll) return ARL_E_RANGE;
-    hipLaunchKernelGGL(ph_uniforms_kernel, dim3((unsigned)(B * ntiles)), dim3(kBlk), 0, (hipStream_t)stream, ph_host_key(seed, call), (int)row0, (int)I, (int)ntiles, out);
-    PH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ph_uniforms_kernel, dim3((unsigned)(B * ntiles)), dim3(kBlk), 0, (hipStream_t)stream, arl_gan_hash_key(seed, call), (int)row0, (int)I, (int)ntiles, out);
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 

@@ -23,12 +23,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "arlib_amd.h"
-
-#define PG_LAUNCH_CHECK()                                   \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
+#include "arl_util.h"
 
 namespace {
 
@@ -43,8 +38,6 @@ constexpr int IS = 64;                           // items per stage of the rows 
 constexpr int TI = 8, FS = 64;                   // items per wave and fake users per stage of the columns backward
 constexpr int kRoundsBlk = 1024;                 // threads of the one workgroup a fake user's rounds run in
 constexpr int kSumBlocks = 1024;                 // partial sums of db2
-
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 // ================================================================================================ pair-MLP head
 __global__ __launch_bounds__(kBlk) void pmlp_fwd_kernel(const float *__restrict__ A, const float *__restrict__ B, const float *__restrict__ w2,
@@ -266,26 +259,13 @@ int pmlp_shape(int64_t F, int64_t I, int64_t H) {
 }
 
 // ================================================================================================ relaxed Gumbel top-k
-__device__ __forceinline__ uint64_t pg_smix(uint64_t x) {      // the splitmix64 finaliser of arl_gan.hip / arl_kernels.hip
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-uint64_t pg_host_key(uint64_t seed, uint64_t call) {            // arl_gan_hash_key's hash of (seed, call)
-    uint64_t x = seed ^ (call * 0x9E3779B97F4A7C15ull);
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t pg_rowkey(uint64_t key, int r, int f) { return pg_smix(key ^ (((uint64_t)(uint32_t)r << 32) | (uint64_t)(uint32_t)f)); }
+__device__ __forceinline__ uint64_t pg_rowkey(uint64_t key, int r, int f) { return arl_splitmix64(key ^ (((uint64_t)(uint32_t)r << 32) | (uint64_t)(uint32_t)f)); }
 
 // g = -log(-log u), u = (n + 1/2) 2^-24 for the 24-bit draw n: u lies in the open interval, so g is finite ([-2.85, 17.4]).  n + 1/2 is exact
 // in fp32 below 2^23; above, -log u = -log1p(-(1 - u)) with 1 - u = (2^24 - 1 - n + 1/2) 2^-24, again exact.
 __device__ __forceinline__ float pg_gumbel(uint64_t rowkey, int i) {
 #pragma clang fp contract(off)
-    const uint32_t n = (uint32_t)(pg_smix(rowkey ^ (uint64_t)(uint32_t)i) >> 40);
+    const uint32_t n = (uint32_t)(arl_splitmix64(rowkey ^ (uint64_t)(uint32_t)i) >> 40);
     float e;
     if (n < 0x800000u) e = -logf(((float)n + 0.5f) * (1.0f / 16777216.0f));
     else e = -log1pf(-(((float)(0xFFFFFFu - n) + 0.5f) * (1.0f / 16777216.0f)));
@@ -438,7 +418,7 @@ int arl_pair_mlp_fwd_f32(const float *A, int64_t F, const float *B, int64_t I, i
     if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)w2 | (uintptr_t)x) & 15) return ARL_E_ARG;
     hipLaunchKernelGGL(pmlp_fwd_kernel, dim3((unsigned)((I + kBlk - 1) / kBlk), (unsigned)((F + TF - 1) / TF)), dim3(kBlk), 0, (hipStream_t)stream, A, B, w2, b2, (int)F,
                        (int)I, (int)H, x);
-    PG_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -460,15 +440,15 @@ int arl_pair_mlp_bwd_f32(const float *g, const float *A, int64_t F, const float 
     const unsigned hb = (unsigned)((H + 63) / 64);
     hipLaunchKernelGGL(pmlp_bwd_rows_kernel, dim3(hb, (unsigned)((F + TF - 1) / TF), (unsigned)ns), dim3(kBlk), 0, st, g, A, B, (int)F, (int)I, (int)H, split_len, partM,
                        partP);
-    PG_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(pmlp_bwd_cols_kernel, dim3((unsigned)((I + kWaves * TI - 1) / (kWaves * TI)), hb), dim3(kBlk), 0, st, g, A, B, w2, (int)F, (int)I, (int)H, dB);
-    PG_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(pmlp_sum_kernel, dim3((unsigned)nsum), dim3(kBlk), 0, st, g, (size_t)F * (size_t)I, sum_part);
-    PG_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(pmlp_dA_kernel, dim3((unsigned)((F * H + kBlk - 1) / kBlk)), dim3(kBlk), 0, st, (const double *)partM, w2, (int)F, (int)H, ns, dA);
-    PG_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL(pmlp_finish_kernel, dim3(hb), dim3(kBlk), 0, st, (const double *)partP, (int)F, (int)H, ns, (const double *)sum_part, nsum, dw2, db2);
-    PG_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -486,23 +466,23 @@ int arl_gumbel_topk_fwd_f32(const float *x, int64_t F, int64_t I, int64_t k, flo
     if (rc != ARL_OK) return rc;
     if (!(tau > 0.f) || (((uintptr_t)x | (uintptr_t)noise | (uintptr_t)S | (uintptr_t)picks | (uintptr_t)lse | (uintptr_t)stats | (uintptr_t)workspace) & 15)) return ARL_E_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const uint64_t key = pg_host_key(seed, call);
+    const uint64_t key = arl_gan_hash_key(seed, call);
     const int ntiles = (int)((I + kBlk - 1) / kBlk);
     const dim3 tiles((unsigned)(F * ntiles));
     if (noise) {
         hipLaunchKernelGGL((gtk_rounds_kernel<false>), dim3((unsigned)F), dim3(kRoundsBlk), 0, st, x, noise, key, (int)F, (int)I, (int)k, tau, (uint32_t *)workspace, picks,
                            lse, stats);
-        PG_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
         hipLaunchKernelGGL((gtk_accum_kernel<false, GTK_S>), tiles, dim3(kBlk), 0, st, x, noise, key, (int)F, (int)I, (int)k, tau, ntiles, (const int32_t *)picks,
                            (const float *)stats, (const float *)nullptr, (const float *)nullptr, S, (float *)nullptr);
     } else {
         hipLaunchKernelGGL((gtk_rounds_kernel<true>), dim3((unsigned)F), dim3(kRoundsBlk), 0, st, x, noise, key, (int)F, (int)I, (int)k, tau, (uint32_t *)workspace, picks,
                            lse, stats);
-        PG_LAUNCH_CHECK();
+        ARL_LAUNCH_CHECK();
         hipLaunchKernelGGL((gtk_accum_kernel<true, GTK_S>), tiles, dim3(kBlk), 0, st, x, noise, key, (int)F, (int)I, (int)k, tau, ntiles, (const int32_t *)picks,
                            (const float *)stats, (const float *)nullptr, (const float *)nullptr, S, (float *)nullptr);
     }
-    PG_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -513,7 +493,7 @@ int arl_gumbel_topk_bwd_f32(const float *x, int64_t F, int64_t I, int64_t k, flo
     if (rc != ARL_OK) return rc;
     if (!(tau > 0.f) || (((uintptr_t)x | (uintptr_t)noise | (uintptr_t)picks | (uintptr_t)stats | (uintptr_t)dS | (uintptr_t)dx | (uintptr_t)workspace) & 15)) return ARL_E_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const uint64_t key = pg_host_key(seed, call);
+    const uint64_t key = arl_gan_hash_key(seed, call);
     const int ntiles = (int)((I + kBlk - 1) / kBlk);
     const dim3 tiles((unsigned)(F * ntiles));
     float *part = (float *)workspace, *c = (float *)((char *)workspace + up16(sizeof(float) * (size_t)F * (size_t)ntiles * (size_t)k));
@@ -521,12 +501,12 @@ int arl_gumbel_topk_bwd_f32(const float *x, int64_t F, int64_t I, int64_t k, flo
     do {                                                                                                                                               \
         hipLaunchKernelGGL((gtk_accum_kernel<HASH, GTK_C>), tiles, dim3(kBlk), 0, st, x, noise, key, (int)F, (int)I, (int)k, tau, ntiles, picks, stats, dS, \
                            (const float *)nullptr, (float *)nullptr, part);                                                                            \
-        PG_LAUNCH_CHECK();                                                                                                                             \
+        ARL_LAUNCH_CHECK();                                                                                                                             \
         hipLaunchKernelGGL(gtk_c_kernel, dim3((unsigned)F), dim3(kBlk), 0, st, (const float *)part, (int)k, ntiles, c);                                \
-        PG_LAUNCH_CHECK();                                                                                                                             \
+        ARL_LAUNCH_CHECK();                                                                                                                             \
         hipLaunchKernelGGL((gtk_accum_kernel<HASH, GTK_DX>), tiles, dim3(kBlk), 0, st, x, noise, key, (int)F, (int)I, (int)k, tau, ntiles, picks, stats, dS, \
                            (const float *)c, dx, (float *)nullptr);                                                                                    \
-        PG_LAUNCH_CHECK();                                                                                                                             \
+        ARL_LAUNCH_CHECK();                                                                                                                             \
     } while (0)
     if (noise) GTK_BWD(false);
     else GTK_BWD(true);
@@ -541,8 +521,8 @@ int arl_gumbel_noise_f32(uint64_t seed, uint64_t call, int64_t k, int64_t F, int
     if (F > 0x7fffffffll || I > kMaxI || F * k * ((I + kBlk - 1) / kBlk) > 0x7fffffffll) return ARL_E_RANGE;
     if ((uintptr_t)out & 15) return ARL_E_ARG;
     const int ntiles = (int)((I + kBlk - 1) / kBlk);
-    hipLaunchKernelGGL(gtk_noise_kernel, dim3((unsigned)(k * F * ntiles)), dim3(kBlk), 0, (hipStream_t)stream, pg_host_key(seed, call), (int)F, (int)I, ntiles, out);
-    PG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(gtk_noise_kernel, dim3((unsigned)(k * F * ntiles)), dim3(kBlk), 0, (hipStream_t)stream, arl_gan_hash_key(seed, call), (int)F, (int)I, ntiles, out);
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 

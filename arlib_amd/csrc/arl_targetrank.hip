@@ -4,9 +4,9 @@
 // the 0-based position of the target in a descending sort of user u's row with ties broken by item id; -1 where (u, targets[t]) is itself masked.
 // The reference's AttackMetric (util/metrics.py:125-208) reads only `rank < k` and `disc[rank]`, so this matrix serves all of its numbers at any k.
 //
-// Rules kept throughout, those of arl_allpairs.hip:
+// Rules kept throughout (the streamed tile is the shared one of arl_stream.h):
 //   * every score is the exact fp32 contraction on v_mfma_f32_16x16x4_f32, and every score that feeds a comparison comes off the SAME instruction
-//     sequence (TRK_MFMA4 over ascending i): the thresholds (pass 1), the stream (pass 2) and the gathered scores of the correction (pass 3).  The
+//     sequence (strm::scores / strm::scores4; the stream's TRK_MFMA4 is the same): the thresholds (pass 1), the stream (pass 2) and the gathered scores of the correction (pass 3).  The
 //     matrix core computes each output element as its own k-ordered fmaf chain, so the score of a pair (u, j) has the same bits in all three.
 //   * pass 1: tscore[u, t] = s[u, targets[t]], the single producer of every threshold;
 //   * pass 2: users resident (16 per wave in registers), items streamed through LDS in 64-row double-buffered stages (optionally in splits of the
@@ -21,18 +21,13 @@
 #include <stdint.h>
 #include <limits.h>
 #include "arlib_amd.h"
-
-#define TRK_LAUNCH_CHECK()                                  \
-    do {                                                    \
-        hipError_t e__ = hipGetLastError();                 \
-        if (e__ != hipSuccess) return (int)e__;             \
-    } while (0)
+#include "arl_stream.h"
 
 namespace {
 
 constexpr int kBlk = 256, kWaves = 4;
 constexpr int kMaxTargets = 64;
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+using strm::f32x4v;
 
 // an int32 that orders as the float does (finite values and infinities); the two zeros share a key
 __device__ __forceinline__ int trk_key(float s) {
@@ -40,15 +35,6 @@ __device__ __forceinline__ int trk_key(float s) {
     b = b == INT_MIN ? 0 : b;
     return b ^ ((b >> 31) & 0x7fffffff);
 }
-
-// the one score sequence: four k-steps of a 16 x 16 tile, A = four consecutive floats of a streamed row, B = the resident row's same four
-#define TRK_MFMA4(SC, A, BR, I)                                                  \
-    do {                                                                         \
-        SC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).x, BR[(I)], SC, 0, 0, 0);     \
-        SC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).y, BR[(I) + 1], SC, 0, 0, 0); \
-        SC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).z, BR[(I) + 2], SC, 0, 0, 0); \
-        SC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).w, BR[(I) + 3], SC, 0, 0, 0); \
-    } while (0)
 
 // Pass 1.  A wave keeps 16 users; the target rows are the A operand straight from memory.  tscore [nU, T].
 template <int D>
@@ -59,23 +45,10 @@ __global__ __launch_bounds__(kBlk) void trk_thresh_kernel(const float *__restric
     const int r0 = (blockIdx.x * kWaves + wv) * 16;
     if (r0 >= nU) return;                                                // the whole wave leaves
     float br[Q];
-    {
-        const int r = min(r0 + c, nU - 1);
-#pragma unroll
-        for (int i = 0; i < Q; i += 4) {
-            const float4 v = *reinterpret_cast<const float4 *>(Pu + (size_t)r * D + Q * g + i);
-            br[i] = v.x; br[i + 1] = v.y; br[i + 2] = v.z; br[i + 3] = v.w;
-        }
-    }
+    strm::load_resident<D>(Pu, min(r0 + c, nU - 1), nU, g, br);
     for (int sub = 0; sub * 16 < T; ++sub) {
         const int item = targets[min(sub * 16 + c, T - 1)];
-        const float *arow = Pi + (size_t)item * D + Q * g;
-        f32x4v sc = f32x4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < Q; i += 4) {
-            const float4 a = *reinterpret_cast<const float4 *>(arow + i);
-            TRK_MFMA4(sc, a, br, i);
-        }
+        const f32x4v sc = strm::scores<D>(Pi + (size_t)item * D + Q * g, br);
         if (r0 + c < nU) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -86,6 +59,16 @@ __global__ __launch_bounds__(kBlk) void trk_thresh_kernel(const float *__restric
     }
 }
 
+// This kernel keeps its own copy of the shared tile (arl_stream.h: load_resident, stage<D>, scores4): built from the shared pieces, <64, 16> measured
+// 0.3 % slower at 1 M x 100 K (370.0 against 369.0 ms, five runs each, this copy's own run-to-run spread 0.5 %) while <64, 32> and <64, 64> measured 0.2 - 0.5 %
+// faster; the instruction mix was the same, the schedule was not.  TRK_MFMA4 is strm::scores' sequence.
+#define TRK_MFMA4(SC, A, BR, I)                                                  \
+    do {                                                                         \
+        SC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).x, BR[(I)], SC, 0, 0, 0);     \
+        SC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).y, BR[(I) + 1], SC, 0, 0, 0); \
+        SC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).z, BR[(I) + 2], SC, 0, 0, 0); \
+        SC = __builtin_amdgcn_mfma_f32_16x16x4f32((A).w, BR[(I) + 3], SC, 0, 0, 0); \
+    } while (0)
 // Pass 2.  part [gridDim.y][nU][T]: the counts of the split's items under the stage rule above.  split_len is a multiple of 64.
 template <int D, int TG>
 __global__ __launch_bounds__(kBlk) void trk_stream_kernel(const float *__restrict__ Pu, int nU, const float *__restrict__ Pi, int nI, int split_len,
@@ -172,6 +155,7 @@ __global__ __launch_bounds__(kBlk) void trk_stream_kernel(const float *__restric
     }
 #undef TRK_FETCH
 #undef TRK_STASH
+#undef TRK_MFMA4
     // the four lane groups of a resident row hold disjoint items
 #pragma unroll
     for (int t = 0; t < TG; ++t) {
@@ -198,11 +182,7 @@ __global__ __launch_bounds__(kBlk) void trk_finish_kernel(const float *__restric
     const int u = blockIdx.x * kWaves + wv;
     if (u >= nU) return;                                                 // the whole wave leaves
     float br[Q];
-#pragma unroll
-    for (int i = 0; i < Q; i += 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(Pu + (size_t)u * D + Q * g + i);
-        br[i] = v.x; br[i + 1] = v.y; br[i + 2] = v.z; br[i + 3] = v.w;
-    }
+    strm::load_resident<D>(Pu, u, nU, g, br);
     int tgt[TT], key[TT], take[TT], listed[TT];
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt) {
@@ -213,22 +193,9 @@ __global__ __launch_bounds__(kBlk) void trk_finish_kernel(const float *__restric
         listed[tt] = 0;
     }
     // scores of the rows it0..it3 (one per tile, this lane's row 16 sub + c) against the user's row
-#define TRK_SCORE64(IT0, IT1, IT2, IT3)                                                               \
-    f32x4v sc0 = f32x4v{0.f, 0.f, 0.f, 0.f}, sc1 = sc0, sc2 = sc0, sc3 = sc0;                             \
-    {                                                                                                 \
-        const float *p0 = Pi + (size_t)(IT0) * D + Q * g, *p1 = Pi + (size_t)(IT1) * D + Q * g;       \
-        const float *p2 = Pi + (size_t)(IT2) * D + Q * g, *p3 = Pi + (size_t)(IT3) * D + Q * g;       \
-        _Pragma("unroll") for (int i = 0; i < Q; i += 4) {                                            \
-            const float4 a0 = *reinterpret_cast<const float4 *>(p0 + i);                              \
-            const float4 a1 = *reinterpret_cast<const float4 *>(p1 + i);                              \
-            const float4 a2 = *reinterpret_cast<const float4 *>(p2 + i);                              \
-            const float4 a3 = *reinterpret_cast<const float4 *>(p3 + i);                              \
-            TRK_MFMA4(sc0, a0, br, i);                                                                \
-            TRK_MFMA4(sc1, a1, br, i);                                                                \
-            TRK_MFMA4(sc2, a2, br, i);                                                                \
-            TRK_MFMA4(sc3, a3, br, i);                                                                \
-        }                                                                                             \
-    }
+#define TRK_SCORE64(IT0, IT1, IT2, IT3)                                                                                               \
+    f32x4v sc[4];                                                                                                                     \
+    strm::scores4<D>(Pi + (size_t)(IT0) * D + Q * g, Pi + (size_t)(IT1) * D + Q * g, Pi + (size_t)(IT2) * D + Q * g, Pi + (size_t)(IT3) * D + Q * g, br, sc);
     // (a) the target's own 64-item stage, where the stream counted >= for every item: take back the target itself (by index) and the later ties
     for (int t = 0; t < T; ++t) {
         const int tg = targets[t], s0 = (tg >> 6) << 6;
@@ -239,7 +206,7 @@ __global__ __launch_bounds__(kBlk) void trk_finish_kernel(const float *__restric
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int item = s0 + 4 * g + j;
-            const int k0 = trk_key(sc0[j]), k1 = trk_key(sc1[j]), k2 = trk_key(sc2[j]), k3 = trk_key(sc3[j]);
+            const int k0 = trk_key(sc[0][j]), k1 = trk_key(sc[1][j]), k2 = trk_key(sc[2][j]), k3 = trk_key(sc[3][j]);
 #define TRK_OWN(ITEM, K) (((ITEM) < nI) && ((ITEM) == tg ? (K) >= kt : ((ITEM) > tg && (K) == kt)) ? 1 : 0)
             v += TRK_OWN(item, k0) + TRK_OWN(item + 16, k1) + TRK_OWN(item + 32, k2) + TRK_OWN(item + 48, k3);
 #undef TRK_OWN
@@ -260,7 +227,7 @@ __global__ __launch_bounds__(kBlk) void trk_finish_kernel(const float *__restric
             for (int j = 0; j < 4; ++j) {
                 const int row = 4 * g + j;                               // lane `row` (c = row, g = 0) fetched this row's item of every tile
                 const int it[4] = {__shfl(i0, row), __shfl(i1, row), __shfl(i2, row), __shfl(i3, row)};
-                const int kk[4] = {trk_key(sc0[j]), trk_key(sc1[j]), trk_key(sc2[j]), trk_key(sc3[j])};
+                const int kk[4] = {trk_key(sc[0][j]), trk_key(sc[1][j]), trk_key(sc[2][j]), trk_key(sc[3][j])};
 #pragma unroll
                 for (int sub = 0; sub < 4; ++sub) {
                     const bool live = kb + 16 * sub + row < k_end;
@@ -307,10 +274,8 @@ void trk_splits(int64_t U, int64_t I, int *n_splits, int *split_len) {
     *n_splits = (int)((I + len - 1) / len);
 }
 
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 bool trk_shape_ok(int64_t U, int64_t I, int64_t d, int64_t T) {
-    return (d == 16 || d == 32 || d == 64 || d == 128) && T >= 1 && T <= kMaxTargets && U >= 1 && I >= 1 && U <= 0x7fffffffll / 128 && I <= 0x7fffffffll / 128;
+    return strm::shape_ok(U, I, d) && T >= 1 && T <= kMaxTargets;
 }
 
 template <int D>
@@ -322,7 +287,7 @@ int trk_run(const float *Pu, int64_t U, const float *Pi, int64_t I, const int32_
     trk_splits(U, I, &ns, &split_len);
     int32_t *part = ns > 1 ? (int32_t *)ws : rank;
     hipLaunchKernelGGL((trk_thresh_kernel<D>), dim3(row_blocks), blk, 0, st, Pu, (int)U, Pi, targets, T, tscore);
-    TRK_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     const dim3 grid(row_blocks, (unsigned)ns);
 #define TRK_STREAM(TG) hipLaunchKernelGGL((trk_stream_kernel<D, TG>), grid, blk, 0, st, Pu, (int)U, Pi, (int)I, split_len, targets, T, (const float *)tscore, part)
     if (T <= 8) TRK_STREAM(8);
@@ -330,10 +295,10 @@ int trk_run(const float *Pu, int64_t U, const float *Pi, int64_t I, const int32_
     else if (T <= 32) TRK_STREAM(32);
     else TRK_STREAM(64);
 #undef TRK_STREAM
-    TRK_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     hipLaunchKernelGGL((trk_finish_kernel<D>), dim3((unsigned)((U + kWaves - 1) / kWaves)), blk, 0, st, Pu, (int)U, Pi, (int)I, targets, T, (const float *)tscore, mptr, mcol,
                        (const int32_t *)part, ns, rank);
-    TRK_LAUNCH_CHECK();
+    ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
 
@@ -357,10 +322,7 @@ int arl_target_rank_f32(const float *Pu, int64_t U, const float *Pi, int64_t I, 
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
 #define TRK_RUN(DD) return trk_run<DD>(Pu, U, Pi, I, targets, (int)T, mask_rowptr, mask_col, rank, tscore, ws, st)
-    if (d == 16) TRK_RUN(16);
-    if (d == 32) TRK_RUN(32);
-    if (d == 64) TRK_RUN(64);
-    TRK_RUN(128);
+    ARL_DISPATCH_WIDTH(d, TRK_RUN);
 #undef TRK_RUN
 }
 
