@@ -7,6 +7,7 @@ import torch
 from conftest import close
 from test_shilling_cpu import attack_args
 import gsp_restatement as rs
+import stream_splits_restatement as splits
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -41,9 +42,11 @@ def restated(Pu, Pi, rowptr, col, val, rw, upstream=1.0):
 
 
 # (R, I, d, positives per row, scale): every width; R and I off the 16 / 64-row tiles; R = 1; (9001, 130) and (20000, 70) split the streamed users
-# 3 and 5 ways; scale 0.6 at d = 64 puts scores near +-12, where sigmoid(-|s|) is within two orders of eps; the last shape has no positives at all
+# 3 and 5 ways (asserted in the test through splits.USER_SPLIT_COUNTS); scale 0.6 at d = 64 puts scores near +-12, where sigmoid(-|s|) is within two
+# orders of eps; (63, 65) has no positives at all; (4097, 65) is the smallest table that splits, 2 x 2049: split 0 ends one row into its 33rd stage
+# and the seam is not a multiple of 4
 SHAPES = [(1, 37, 16, 3, 0.3), (130, 77, 16, 5, 0.3), (1000, 333, 32, 10, 0.2), (777, 1682, 64, 20, 0.1), (2049, 515, 128, 4, 0.1),
-          (9001, 130, 64, 5, 0.15), (20000, 70, 32, 2, 0.2), (257, 130, 64, 6, 0.6), (63, 65, 128, 0, 0.1)]
+          (9001, 130, 64, 5, 0.15), (20000, 70, 32, 2, 0.2), (257, 130, 64, 6, 0.6), (63, 65, 128, 0, 0.1), (4097, 65, 32, 3, 0.2)]
 FACTOR, FLOOR = 4.0, 1e-6
 NAMES = ('loss', 'rowloss', 'dPu', 'dPi')
 
@@ -55,6 +58,7 @@ def test_kernel_against_float64(R, I, d, per_row, scale, weighted):
     FLOOR = 1e-6 where the composed route lands closer than that; max-norm relative error of loss, rowloss, dPu and dPi.  Measured on the MI355X,
     worst case over SHAPES: see DESIGN.md section 3j."""
     from arlib_amd import ops
+    assert splits.split_count(I, R)[0] == splits.USER_SPLIT_COUNTS.get((R, I), 1)          # the streamed users' splits this shape is here for
     host = problem(R, I, d, per_row, scale, seed=R + I, weighted=weighted)
     want = restated(*host)
     if scale > 0.5:

@@ -10,6 +10,7 @@ from conftest import golden
 from test_host_api import make_data
 from test_shilling_cpu import attack_args, reseed, block, sha
 from legup_restatement import colsoftmax_target_loss as restated
+import stream_splits_restatement as splits
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -28,10 +29,12 @@ def problem(U, I, d, T, scale, seed):
     return Pu.to(DEV), Pi.to(DEV), cols
 
 
-# every width; U and I off the 16 / 64-row tiles; T = 1 and 5; U = 1; (9001, 130) and (20000, 70) split the streamed users 3 and 5 ways;
-# scale 1.5 at d = 64 puts scores past 88.7, where a plain fp32 exp is inf and only the running maximum keeps the sums finite
+# every width; U and I off the 16 / 64-row tiles; T = 1 and 5; U = 1; (9001, 130) and (20000, 70) split the streamed users 3 and 5 ways (asserted in
+# the test through splits.USER_SPLIT_COUNTS); scale 1.5 at d = 64 puts scores past 88.7, where a plain fp32 exp is inf and only the running maximum
+# keeps the sums finite; (4097, 65) is the smallest table that splits, 2 x 2049: split 0 ends one row into its 33rd stage and the seam is not a
+# multiple of 4
 SHAPES = [(1, 37, 16, 1, 0.3), (130, 77, 16, 5, 0.3), (1000, 333, 32, 5, 0.2), (777, 1682, 64, 5, 0.1), (2049, 515, 128, 1, 0.1),
-          (9001, 130, 64, 5, 0.15), (20000, 70, 32, 1, 0.2), (1500, 900, 64, 5, 1.5), (63, 65, 128, 5, 0.1)]
+          (9001, 130, 64, 5, 0.15), (20000, 70, 32, 1, 0.2), (1500, 900, 64, 5, 1.5), (63, 65, 128, 5, 0.1), (4097, 65, 32, 5, 0.2)]
 FACTOR, FLOOR = 4.0, 1e-6
 
 
@@ -41,6 +44,7 @@ def test_kernel_against_float64(U, I, d, T, scale):
     the composed route happens to land closer than that.  Measured on the MI355X (max-norm relative error, kernel / composed), worst case over SHAPES:
     see DESIGN.md section 3f."""
     from arlib_amd import ops
+    assert splits.split_count(I, U)[0] == splits.USER_SPLIT_COUNTS.get((U, I), 1)      # the streamed users' splits this shape is here for
     Pu, Pi, cols = problem(U, I, d, T, scale, seed=U + I)
     want = restated(Pu.cpu().numpy(), Pi.cpu().numpy(), cols, want_grad=True)
     if scale > 1:

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 import multvae_restatement as R
+import stream_splits_restatement as splits
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -77,6 +78,8 @@ def on_device(B, I, d, kind='plain', weighted=False):
 @pytest.mark.parametrize('B,I,d', SHAPES)
 def test_kernel_against_float64(B, I, d, kind, weighted):
     from arlib_amd import ops
+    # (130, 1030) streams the items in 2 splits and (33, 4099) in 5; no shape here splits the batch rows (test_gpu_stream_splits.py does)
+    assert splits.stage_splits(B, I) == splits.ITEM_SPLITS.get((B, I), (1, (I + 63) // 64 * 64)) and splits.stage_splits(I, B)[0] == 1
     q, E, P, g = on_device(B, I, d, kind, weighted)
     want = float64(B, I, d, kind, weighted)
     if kind == 'dominant' and I > 100:

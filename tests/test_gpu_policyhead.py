@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 import poisonrec_restatement as rs
+import stream_splits_restatement as splits
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -84,6 +85,10 @@ CASES = [(B, I, d, kind, 'random') for (B, I, d) in SHAPES for kind in ('plain',
 @pytest.mark.parametrize('B,I,d,kind,acts', CASES)
 def test_eval_against_float64(B, I, d, kind, acts):
     from arlib_amd import ops
+    # (130, 1030) streams the items in 2 splits and (33, 4099) in 5, in the statistics passes and in dq alike; no shape here splits the batch rows
+    # (test_gpu_stream_splits.py does)
+    assert splits.ph_item_splits(I) == splits.stage_splits(B, I) == splits.ITEM_SPLITS.get((B, I), (1, (I + 63) // 64 * 64))
+    assert splits.stage_splits(I, B)[0] == 1
     q, E, words, gl, ge, _ = on_device(B, I, d, kind, acts)
     logp64, ent64, dq64, dE64, p64 = float64(B, I, d, kind, acts)
     if kind == 'dominant' and I > 100:

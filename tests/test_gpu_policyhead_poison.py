@@ -6,12 +6,14 @@ import inspect
 import pytest
 import torch
 import poison
+import stream_splits_restatement as splits
 from test_gpu_poisoned_memory import introspected
 from test_gpu_policyhead import on_device
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
-SHAPES = [(3, 77, 16), (70, 4099, 64)]
+SPLIT = splits.BOTH_SPLIT_SHAPE                                        # part_ms, part_sum, part_dq and part_dE with more than one split each
+SHAPES = [(3, 77, 16), (70, 4099, 64), SPLIT]
 SEED, CALL = 99, 2
 
 
@@ -54,6 +56,7 @@ def test_every_allocating_op_of_the_module_has_a_case():
 @pytest.mark.parametrize('grad', [False, True])
 def test_op_is_independent_of_scratch_memory(name, B, I, d, grad):
     from arlib_amd import policyhead as ph
+    assert (splits.stage_splits(I, B)[0] > 1) == ((B, I, d) == SPLIT) and (splits.ph_item_splits(I)[0] > 1) == (I > 1024)
     P = inputs(B, I, d)
     clean = CASES[name](ph, P, grad)
     with poison.poisoned_allocations():
@@ -65,11 +68,13 @@ def test_op_is_independent_of_scratch_memory(name, B, I, d, grad):
 def test_workspace_reused_between_shapes():
     """The caching allocator hands the second call the first call's blocks (more splits, more action words): results equal a fresh process's."""
     from arlib_amd import policyhead as ph
-    big, small = inputs(70, 4099, 64), inputs(3, 77, 16)
+    big, split, small = inputs(70, 4099, 64), inputs(*SPLIT), inputs(3, 77, 16)
+    assert splits.ph_item_splits(SPLIT[1])[0] == splits.stage_splits(SPLIT[0], SPLIT[1])[0] == 3 and splits.stage_splits(SPLIT[1], SPLIT[0])[0] == 2
 
     def run(P):
         return (CASES['bernoulli_softmax_eval'](ph, P, True), CASES['bernoulli_softmax_sample'](ph, P, True), CASES['bernoulli_softmax_sample'](ph, P, False))
     torch.cuda.empty_cache()
     alone = run(small)
     run(big)
+    run(split)
     assert poison.compare(alone, run(small)) == []
