@@ -152,6 +152,12 @@ _SIGS = {
     'arl_als_gram_f64': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     'arl_als_solve_rows_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
     'arl_als_solve_rows_f32': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, C.c_double, C.c_double, _i64, _vp, _vp, _vp]),
+    'arl_als_solve_rows_target_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'arl_als_solve_rows_target_f32': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, C.c_double, C.c_double, _i32, _i64, _vp, _vp, _vp]),
+    'arl_als_default_col_split_len': (_i64, []),
+    'arl_als_adjoint_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    'arl_als_adjoint_f32': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i32, _i64, _i64, _vp, _vp,
+                                      _vp, _vp]),
     'arl_als_objective_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'arl_als_objective_f64': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     'arl_kmeans_assign_f32':(C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),

@@ -28,6 +28,7 @@ namespace {
 
 constexpr int kBlk = 256, kWaves = 4, kStage = 64;
 constexpr int kDefaultSplit = 8192;
+constexpr int kDefaultColSplit = 1024;                   // the adjoint's column pass: columns longer than this are cut into pieces
 constexpr int kGramSpans = 256, kGramSpanRows = 128, kGramStage = 32;
 constexpr int kPlanBlk = 1024;
 constexpr int kSumParts = 256;
@@ -149,8 +150,9 @@ __device__ __forceinline__ bool als_pair(int p, int np, int &ti, int &tj) {
 }
 
 // The entries [lo, hi) of the CSR (hi > lo): sv[k][reg] = the wave's tiles of S = sum w y y^T (element (16 ti + 4 g + reg, 16 tj + c) of tile k), and
-// bv = element tid of b = sum (1 + alpha w) y on the threads tid < D.  Ends with the workgroup synchronised and the staging image free.
-template <int D>
+// bv = element tid of b = sum beta(w) y on the threads tid < D.  Ends with the workgroup synchronised and the staging image free.  RULE is the target
+// rule: 0 ('stored') beta(w) = 1 + alpha w, 1 ('relaxed') beta(w) = (1 + alpha) w -- the same double at w = 1, nothing at w = 0.
+template <int D, int RULE = 0>
 __device__ __forceinline__ void als_accumulate(const float *__restrict__ Y, const int32_t *__restrict__ col, const float *__restrict__ val, int lo, int hi,
                                                double alpha, unsigned char *smem, double (&sv)[als_cfg<D>::PW][4], double &bv) {
 #pragma clang fp contract(off)
@@ -221,7 +223,8 @@ __device__ __forceinline__ void als_accumulate(const float *__restrict__ Y, cons
         for (int k = 0; k < PW; ++k)
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) sv[k][reg] += (double)acc[k][reg];
-        for (int r = bpartid; r < kStage; r += NPART) bacc += (1.0 + alpha * (double)W[r]) * (double)T[r * LD + bcol];
+        for (int r = bpartid; r < kStage; r += NPART)
+            bacc += (RULE == 0 ? 1.0 + alpha * (double)W[r] : (1.0 + alpha) * (double)W[r]) * (double)T[r * LD + bcol];
         if (st + 1 < nst) ALS_STASH(buf ^ 1);
         __syncthreads();
     }
@@ -238,7 +241,7 @@ __device__ __forceinline__ void als_accumulate(const float *__restrict__ Y, cons
 }
 
 // One workgroup per piece of a split row: the piece's tiles (fp32, [pair][lane][reg]) and b (double).
-template <int D>
+template <int D, int RULE = 0>
 __global__ __launch_bounds__(kBlk) void als_piece_kernel(const float *__restrict__ Y, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                           const float *__restrict__ val, const int32_t *__restrict__ rows, int n_solve, int split_len,
                                                           int max_pieces, double alpha, const int32_t *__restrict__ piece_off, unsigned char *__restrict__ parts) {
@@ -256,7 +259,7 @@ __global__ __launch_bounds__(kBlk) void als_piece_kernel(const float *__restrict
     const int r = rows ? rows[j] : j;
     const int lo = rowptr[r] + (p - piece_off[j]) * split_len, hi = min(rowptr[r + 1], lo + split_len);
     double sv[cfg::PW][4], bv;
-    als_accumulate<D>(Y, col, val, lo, hi, alpha, smem, sv, bv);
+    als_accumulate<D, RULE>(Y, col, val, lo, hi, alpha, smem, sv, bv);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     float *pt = reinterpret_cast<float *>(parts + (size_t)p * cfg::piece_bytes);
     double *pb = reinterpret_cast<double *>(parts + (size_t)p * cfg::piece_bytes + sizeof(float) * cfg::NP * 256);
@@ -275,11 +278,12 @@ __device__ __forceinline__ double als_readlane(double v, int src) {      // src 
 }
 
 // One workgroup per listed row: (S, b) from the row's entries or from its pieces, A = G + alpha S + lambda I in LDS, Cholesky, the two substitutions.
-template <int D>
+// ADJ: the row adjoint z_r = A_r^-1 g_r -- the same A_r, with row j of gX travelling where b_r travels; X then receives z.
+template <int D, int RULE = 0, bool ADJ = false>
 __global__ __launch_bounds__(kBlk) void als_row_kernel(const float *__restrict__ Y, const double *__restrict__ G, const int32_t *__restrict__ rowptr,
                                                         const int32_t *__restrict__ col, const float *__restrict__ val, const int32_t *__restrict__ rows,
                                                         int n_solve, int max_pieces, double alpha, double lambda, const int32_t *__restrict__ piece_off,
-                                                        const unsigned char *__restrict__ parts, float *__restrict__ X) {
+                                                        const unsigned char *__restrict__ parts, float *__restrict__ X, const float *__restrict__ gX) {
     typedef als_cfg<D> cfg;
     constexpr int PW = cfg::PW, TPR = kBlk / D;
     __shared__ __attribute__((aligned(16))) unsigned char smem[cfg::smem_bytes];
@@ -313,8 +317,9 @@ __global__ __launch_bounds__(kBlk) void als_row_kernel(const float *__restrict__
             if (tid < D) bv += pb[tid];
         }
     } else {
-        als_accumulate<D>(Y, col, val, lo, hi, alpha, smem, sv, bv);
+        als_accumulate<D, RULE>(Y, col, val, lo, hi, alpha, smem, sv, bv);
     }
+    if (ADJ) bv = tid < D ? (double)gX[(size_t)j * D + tid] : 0.0;
     // the solve image (the staging image is free: als_accumulate ends synchronised)
     double *Lp = reinterpret_cast<double *>(smem);                       // packed lower triangle: (i, k) at i (i + 1) / 2 + k
     double *zb = Lp + (size_t)D * (D + 1) / 2;                            // the b row, L^-1 b once the factorisation is through
@@ -457,6 +462,164 @@ __global__ __launch_bounds__(kBlk) void als_fold_kernel(const double *__restrict
     if (threadIdx.x == 0) out[0] = red[0];
 }
 
+// ------------------------------------------------------------------------------------------------ the adjoint of the row solve
+// Given g_r = dL/dx_r and z_r = A_r^-1 g_r (als_row_kernel<D, 0, true>), with s = x_r . y_i, t = z_r . y_i, beta(w) = b0 + b1 w and C = sum_r z_r x_r^T:
+//     dL/dw_ri = t (b1 - alpha s)
+//     dL/dy_i  = sum_{r with i} [ (beta(w_ri) - alpha w_ri s) z_r - alpha w_ri t x_r ]  -  y_i (C + C^T)
+// Entry pass: coef [e] = (beta - alpha w s, -alpha w t) and dval [e], one wave per row, the dots in double as in als_obj_rows_kernel.
+template <int D>
+__global__ __launch_bounds__(kBlk) void alsgrad_entry_kernel(const float *__restrict__ X, const float *__restrict__ Z, int n_rows, const float *__restrict__ Y,
+                                                              const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+                                                              double alpha, double b0, double b1, double2 *__restrict__ coef, float *__restrict__ dval) {
+    __shared__ double xs[kWaves][D], zs[kWaves][D];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, u_ = blockIdx.x * kWaves + wv;
+    const bool act = u_ < n_rows;
+    const int u = act ? u_ : n_rows - 1;                                 // a wave past the end loads the last row and writes nothing
+    for (int i = lane; i < D; i += 64) { xs[wv][i] = (double)X[(size_t)u * D + i]; zs[wv][i] = (double)Z[(size_t)u * D + i]; }
+    __syncthreads();
+    const double *x = xs[wv], *z = zs[wv];
+    const int lo = rowptr[u], hi = act ? rowptr[u + 1] : lo;
+    for (int e = lo + lane; e < hi; e += 64) {
+        const float *y = Y + (size_t)col[e] * D;
+        double s = 0.0, t = 0.0;
+#pragma unroll 2
+        for (int k = 0; k < D; k += 4) {
+            const float4 v = *reinterpret_cast<const float4 *>(y + k);
+            s += x[k] * (double)v.x; s += x[k + 1] * (double)v.y; s += x[k + 2] * (double)v.z; s += x[k + 3] * (double)v.w;
+            t += z[k] * (double)v.x; t += z[k + 1] * (double)v.y; t += z[k + 2] * (double)v.z; t += z[k + 3] * (double)v.w;
+        }
+        const double w = val ? (double)val[e] : 1.0;
+        coef[e] = make_double2((b0 + b1 * w) - alpha * w * s, -(alpha * w * t));
+        if (dval) dval[e] = (float)(t * (b1 - alpha * s));
+    }
+}
+
+// part [span][D * D] = sum over the span's rows, ascending, of z x^T in double: als_gram_partial_kernel with two tables.
+template <int D>
+__global__ __launch_bounds__(kBlk) void alsgrad_xgram_partial_kernel(const float *__restrict__ Z, const float *__restrict__ X, int n, int span,
+                                                                      double *__restrict__ part) {
+    constexpr int R = D / 16, Q = D / 4;
+    __shared__ float tz[kGramStage * D], tx_[kGramStage * D];
+    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
+    const int r_begin = blockIdx.x * span, r_end = min(n, r_begin + span);
+    double acc[R][R];
+#pragma unroll
+    for (int a = 0; a < R; ++a)
+#pragma unroll
+        for (int b = 0; b < R; ++b) acc[a][b] = 0.0;
+    for (int r0 = r_begin; r0 < r_end; r0 += kGramStage) {
+        for (int idx = tid; idx < kGramStage * Q; idx += kBlk) {
+            const int row = idx / Q, q = (idx % Q) * 4;
+            float4 vz = make_float4(0.f, 0.f, 0.f, 0.f), vx = vz;                  // rows past the span add exact zeros
+            if (r0 + row < r_end) {
+                vz = *reinterpret_cast<const float4 *>(Z + (size_t)(r0 + row) * D + q);
+                vx = *reinterpret_cast<const float4 *>(X + (size_t)(r0 + row) * D + q);
+            }
+            *reinterpret_cast<float4 *>(&tz[row * D + q]) = vz;
+            *reinterpret_cast<float4 *>(&tx_[row * D + q]) = vx;
+        }
+        __syncthreads();
+        for (int rr = 0; rr < kGramStage; ++rr) {
+            double za[R], xb[R];
+#pragma unroll
+            for (int a = 0; a < R; ++a) { za[a] = (double)tz[rr * D + ty + 16 * a]; xb[a] = (double)tx_[rr * D + tx + 16 * a]; }
+#pragma unroll
+            for (int a = 0; a < R; ++a)
+#pragma unroll
+                for (int b = 0; b < R; ++b) acc[a][b] += za[a] * xb[b];
+        }
+        __syncthreads();
+    }
+    double *out = part + (size_t)blockIdx.x * D * D;
+#pragma unroll
+    for (int a = 0; a < R; ++a)
+#pragma unroll
+        for (int b = 0; b < R; ++b) out[(ty + 16 * a) * D + tx + 16 * b] = acc[a][b];
+}
+
+// Cs [i][j] = C [i][j] + C [j][i], each C element the spans' partials in span order: symmetric bit for bit.
+__global__ __launch_bounds__(kBlk) void alsgrad_xgram_fold_kernel(const double *__restrict__ part, int ns, int d, double *__restrict__ Cs) {
+    const int e = blockIdx.x * kBlk + threadIdx.x, dd = d * d;
+    if (e >= dd) return;
+    const int et = (e % d) * d + e / d;
+    double v = part[e], vt = part[et];
+    for (int s = 1; s < ns; ++s) { v += part[(size_t)s * dd + e]; vt += part[(size_t)s * dd + et]; }
+    Cs[e] = v + vt;
+}
+
+// Element tid (on the threads tid < D) of sum_e (coef[tperm[e]].x z_row + coef[tperm[e]].y x_row) over the entries [lo, hi) of the transposed order:
+// thread group g of the kBlk / D groups takes the entries lo + g, lo + g + groups, ... in ascending order, the groups are added in group order.
+template <int D>
+__device__ __forceinline__ double alsgrad_col_sum(const float *__restrict__ Z, const float *__restrict__ X, const int32_t *__restrict__ trow,
+                                                  const int32_t *__restrict__ tperm, const double2 *__restrict__ coef, int lo, int hi, double *red) {
+    constexpr int NPART = kBlk / D;
+    const int tid = threadIdx.x, k = tid % D, part = tid / D;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int e = lo + part; e < hi; e += NPART) {
+        const size_t r = (size_t)trow[e] * D + k;
+        const double2 c = coef[tperm[e]];
+        acc += c.x * (double)Z[r] + c.y * (double)X[r];
+    }
+    red[tid] = acc;
+    __syncthreads();
+    double v = 0.0;
+    if (tid < D) {
+#pragma unroll
+        for (int p = 0; p < NPART; ++p) v += red[p * D + tid];
+    }
+    __syncthreads();
+    return v;
+}
+
+// One workgroup per piece of a split column: its partial sum, D doubles.
+template <int D>
+__global__ __launch_bounds__(kBlk) void alsgrad_colpiece_kernel(const float *__restrict__ Z, const float *__restrict__ X, const int32_t *__restrict__ tptr,
+                                                                 const int32_t *__restrict__ trow, const int32_t *__restrict__ tperm,
+                                                                 const double2 *__restrict__ coef, int n, int split_len, int max_pieces,
+                                                                 const int32_t *__restrict__ piece_off, double *__restrict__ cparts) {
+    __shared__ double red[kBlk];
+    const int p = blockIdx.x;
+    if (p >= piece_off[n] || p >= max_pieces) return;
+    int a = 0, b = n + 1;                                                // the first index whose offset exceeds p; the column is the one before it
+    while (a < b) {
+        const int m = (a + b) >> 1;
+        if (piece_off[m] > p) b = m; else a = m + 1;
+    }
+    const int i = a - 1;
+    if (piece_off[i + 1] > max_pieces) return;                           // a column whose pieces do not all fit the workspace is summed unsplit
+    const int lo = tptr[i] + (p - piece_off[i]) * split_len, hi = min(tptr[i + 1], lo + split_len);
+    const double v = alsgrad_col_sum<D>(Z, X, trow, tperm, coef, lo, hi, red);
+    if ((int)threadIdx.x < D) cparts[(size_t)p * D + threadIdx.x] = v;
+}
+
+// One workgroup per row i of Y: dY_i = the column's sum (from its entries, or from its pieces in piece order) - y_i Cs.
+template <int D>
+__global__ __launch_bounds__(kBlk) void alsgrad_col_kernel(const float *__restrict__ Y, const float *__restrict__ Z, const float *__restrict__ X,
+                                                            const int32_t *__restrict__ tptr, const int32_t *__restrict__ trow, const int32_t *__restrict__ tperm,
+                                                            const double2 *__restrict__ coef, const double *__restrict__ Cs, int max_pieces,
+                                                            const int32_t *__restrict__ piece_off, const double *__restrict__ cparts, float *__restrict__ dY) {
+    __shared__ double red[kBlk];
+    __shared__ double ys[D];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const int lo = tptr[i], hi = tptr[i + 1];
+    const int p0 = piece_off[i], p1 = piece_off[i + 1];
+    if (tid < D) ys[tid] = (double)Y[(size_t)i * D + tid];
+    double v = 0.0;
+    if (p1 > p0 && p1 <= max_pieces) {                                   // workgroup-uniform
+        if (tid < D)
+            for (int p = p0; p < p1; ++p) v += cparts[(size_t)p * D + tid];
+    } else if (hi > lo) {
+        v = alsgrad_col_sum<D>(Z, X, trow, tperm, coef, lo, hi, red);
+    }
+    __syncthreads();
+    if (tid >= D) return;
+    double g = 0.0;
+#pragma unroll 4
+    for (int j = 0; j < D; ++j) g += ys[j] * Cs[(size_t)j * D + tid];
+    dY[(size_t)i * D + tid] = (float)(v - g);
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 bool als_width(int64_t d) { return d == 16 || d == 32 || d == 64 || d == 128; }
 bool als_rows_ok(int64_t n) { return n > 0 && n <= 0x7fffffffll / 128; }
@@ -475,21 +638,74 @@ int64_t als_max_pieces(int64_t n_solve, int64_t nnz_listed, int64_t split_len) {
 
 int64_t als_split(int64_t split_len) { return split_len > 0 ? split_len : kDefaultSplit; }
 
-template <int D>
+template <int D, int RULE = 0, bool ADJ = false>
 int als_solve_run(const float *Y, const double *G, const int32_t *rowptr, const int32_t *col, const float *val, const int32_t *rows, int64_t n_solve,
-                  int64_t nnz_listed, double alpha, double lambda, int64_t split_len, float *X, char *ws, hipStream_t st) {
+                  int64_t nnz_listed, double alpha, double lambda, int64_t split_len, float *X, char *ws, hipStream_t st, const float *gX = nullptr) {
     const int64_t mp = als_max_pieces(n_solve, nnz_listed, split_len);
     int32_t *piece_off = (int32_t *)ws;
     unsigned char *parts = (unsigned char *)(ws + up16(sizeof(int32_t) * (size_t)(n_solve + 1)));
     hipLaunchKernelGGL(als_plan_kernel, dim3(1), dim3(kPlanBlk), 0, st, rowptr, rows, (int)n_solve, (int)split_len, piece_off);
     ARL_LAUNCH_CHECK();
     if (mp > 0) {
-        hipLaunchKernelGGL((als_piece_kernel<D>), dim3((unsigned)mp), dim3(kBlk), 0, st, Y, rowptr, col, val, rows, (int)n_solve, (int)split_len, (int)mp, alpha,
+        hipLaunchKernelGGL((als_piece_kernel<D, RULE>), dim3((unsigned)mp), dim3(kBlk), 0, st, Y, rowptr, col, val, rows, (int)n_solve, (int)split_len, (int)mp, alpha,
                            (const int32_t *)piece_off, parts);
         ARL_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL((als_row_kernel<D>), dim3((unsigned)n_solve), dim3(kBlk), 0, st, Y, G, rowptr, col, val, rows, (int)n_solve, (int)mp, alpha, lambda,
-                       (const int32_t *)piece_off, (const unsigned char *)parts, X);
+    hipLaunchKernelGGL((als_row_kernel<D, RULE, ADJ>), dim3((unsigned)n_solve), dim3(kBlk), 0, st, Y, G, rowptr, col, val, rows, (int)n_solve, (int)mp, alpha,
+                       lambda, (const int32_t *)piece_off, (const unsigned char *)parts, X, gX);
+    ARL_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
+int64_t alsgrad_col_split(int64_t col_split_len) { return col_split_len > 0 ? col_split_len : kDefaultColSplit; }
+
+// the adjoint's workspace: the row solve's (piece plan, pieces), z, the entries' coefficients, the cross-Gram's partials and C + C^T, the columns' piece
+// plan and pieces
+struct alsgrad_ws { size_t solve, z, coef, xpart, cs, cplan, cparts, total; int64_t max_cpieces; };
+alsgrad_ws alsgrad_layout(int64_t n, int64_t n_rows, int64_t nnz, int64_t d, int64_t split_len, int64_t col_split_len) {
+    alsgrad_ws w;
+    size_t o = 0;
+    w.solve = o; o += up16(up16(sizeof(int32_t) * (size_t)(n_rows + 1)) + (size_t)als_max_pieces(n_rows, nnz, split_len) * als_piece_bytes(d));
+    w.z = o;     o += up16(sizeof(float) * (size_t)n_rows * (size_t)d);
+    w.coef = o;  o += up16(sizeof(double2) * (size_t)nnz);
+    w.xpart = o; o += up16(sizeof(double) * (size_t)gram_splits(n_rows).ns * (size_t)d * (size_t)d);
+    w.cs = o;    o += up16(sizeof(double) * (size_t)d * (size_t)d);
+    w.cplan = o; o += up16(sizeof(int32_t) * (size_t)(n + 1));
+    w.max_cpieces = als_max_pieces(n, nnz, col_split_len);
+    w.cparts = o; o += up16(sizeof(double) * (size_t)w.max_cpieces * (size_t)d);
+    w.total = o;
+    return w;
+}
+
+template <int D>
+int alsgrad_run(const float *Y, int64_t n, const double *G, const int32_t *rowptr, const int32_t *col, const float *val, int64_t n_rows, int64_t nnz,
+                const float *X, const float *gX, const int32_t *tptr, const int32_t *trow, const int32_t *tperm, double alpha, double lambda, double b0,
+                double b1, int64_t split_len, int64_t col_split_len, float *dY, float *dval, char *ws, hipStream_t st) {
+    const alsgrad_ws w = alsgrad_layout(n, n_rows, nnz, D, split_len, col_split_len);
+    float *Z = (float *)(ws + w.z);
+    double2 *coef = (double2 *)(ws + w.coef);
+    double *xpart = (double *)(ws + w.xpart), *Cs = (double *)(ws + w.cs), *cparts = (double *)(ws + w.cparts);
+    int32_t *cplan = (int32_t *)(ws + w.cplan);
+    // z_r = A_r^-1 g_r: the forward's launches with g as the extra row
+    const int rc = als_solve_run<D, 0, true>(Y, G, rowptr, col, val, nullptr, n_rows, nnz, alpha, lambda, split_len, Z, ws + w.solve, st, gX);
+    if (rc != ARL_OK) return rc;
+    hipLaunchKernelGGL((alsgrad_entry_kernel<D>), dim3((unsigned)((n_rows + kWaves - 1) / kWaves)), dim3(kBlk), 0, st, X, (const float *)Z, (int)n_rows, Y, rowptr,
+                       col, val, alpha, b0, b1, coef, dval);
+    ARL_LAUNCH_CHECK();
+    const gram_split gs = gram_splits(n_rows);
+    hipLaunchKernelGGL((alsgrad_xgram_partial_kernel<D>), dim3((unsigned)gs.ns), dim3(kBlk), 0, st, (const float *)Z, X, (int)n_rows, gs.span, xpart);
+    ARL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(alsgrad_xgram_fold_kernel, dim3((unsigned)((D * D + kBlk - 1) / kBlk)), dim3(kBlk), 0, st, (const double *)xpart, gs.ns, D, Cs);
+    ARL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(als_plan_kernel, dim3(1), dim3(kPlanBlk), 0, st, tptr, (const int32_t *)nullptr, (int)n, (int)col_split_len, cplan);
+    ARL_LAUNCH_CHECK();
+    if (w.max_cpieces > 0) {
+        hipLaunchKernelGGL((alsgrad_colpiece_kernel<D>), dim3((unsigned)w.max_cpieces), dim3(kBlk), 0, st, (const float *)Z, X, tptr, trow, tperm,
+                           (const double2 *)coef, (int)n, (int)col_split_len, (int)w.max_cpieces, (const int32_t *)cplan, cparts);
+        ARL_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL((alsgrad_col_kernel<D>), dim3((unsigned)n), dim3(kBlk), 0, st, Y, (const float *)Z, X, tptr, trow, tperm, (const double2 *)coef,
+                       (const double *)Cs, (int)w.max_cpieces, (const int32_t *)cplan, (const double *)cparts, dY);
     ARL_LAUNCH_CHECK();
     return ARL_OK;
 }
@@ -546,6 +762,65 @@ int arl_als_solve_rows_f32(const float *Y, int64_t n, int64_t d, const double *G
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
 #define ALS_RUN(DD) return als_solve_run<DD>(Y, G, rowptr, col, val, rows, n_solve, nnz_listed, alpha, lambda, split_len, X, ws, st)
+    if (d == 16) ALS_RUN(16);
+    if (d == 32) ALS_RUN(32);
+    if (d == 64) ALS_RUN(64);
+    ALS_RUN(128);
+#undef ALS_RUN
+}
+
+int64_t arl_als_solve_rows_target_workspace_bytes(int64_t n_solve, int64_t nnz_listed, int64_t d, int64_t split_len) {
+    return arl_als_solve_rows_workspace_bytes(n_solve, nnz_listed, d, split_len);
+}
+
+int arl_als_solve_rows_target_f32(const float *Y, int64_t n, int64_t d, const double *G, const int32_t *rowptr, const int32_t *col, const float *val,
+                                  int64_t n_rows, const int32_t *rows, int64_t n_solve, int64_t nnz_listed, double alpha, double lambda, int32_t target,
+                                  int64_t split_len, float *X, void *workspace, arl_stream_t stream) {
+    if (target == ARL_ALS_TARGET_STORED)                                 // the same launches: the same bits
+        return arl_als_solve_rows_f32(Y, n, d, G, rowptr, col, val, n_rows, rows, n_solve, nnz_listed, alpha, lambda, split_len, X, workspace, stream);
+    if (!Y || !G || !rowptr || !col || !X || !workspace) return ARL_E_NULL;
+    if (!als_width(d)) return ARL_E_DIM;
+    if (target != ARL_ALS_TARGET_RELAXED) return ARL_E_ARG;
+    if (n <= 0 || n_rows <= 0 || n_solve <= 0 || nnz_listed < 0 || !(alpha >= 0.0) || !(lambda >= 0.0)) return ARL_E_ARG;
+    if (!als_rows_ok(n) || !als_rows_ok(n_solve) || n_rows > 0x7fffffffll - 1 || nnz_listed > 0x7fffffffll) return ARL_E_RANGE;
+    if (((uintptr_t)Y | (uintptr_t)G | (uintptr_t)X | (uintptr_t)workspace) & 15) return ARL_E_ARG;
+    split_len = als_split(split_len);
+    if (split_len > 0x7fffffffll) split_len = 0x7fffffffll;
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+#define ALS_RUN(DD) return als_solve_run<DD, 1>(Y, G, rowptr, col, val, rows, n_solve, nnz_listed, alpha, lambda, split_len, X, ws, st)
+    if (d == 16) ALS_RUN(16);
+    if (d == 32) ALS_RUN(32);
+    if (d == 64) ALS_RUN(64);
+    ALS_RUN(128);
+#undef ALS_RUN
+}
+
+int64_t arl_als_default_col_split_len(void) { return kDefaultColSplit; }
+
+int64_t arl_als_adjoint_workspace_bytes(int64_t n, int64_t n_rows, int64_t nnz, int64_t d, int64_t split_len, int64_t col_split_len) {
+    if (!als_width(d) || !als_rows_ok(n) || !als_rows_ok(n_rows) || nnz <= 0 || nnz > 0x7fffffffll) return 0;
+    return (int64_t)alsgrad_layout(n, n_rows, nnz, d, als_split(split_len), alsgrad_col_split(col_split_len)).total;
+}
+
+int arl_als_adjoint_f32(const float *Y, int64_t n, int64_t d, const double *G, const int32_t *rowptr, const int32_t *col, const float *val, int64_t n_rows,
+                        int64_t nnz, const float *X, const float *gX, const int32_t *tptr, const int32_t *trow, const int32_t *tperm, double alpha,
+                        double lambda, int32_t target, int64_t split_len, int64_t col_split_len, float *dY, float *dval, void *workspace,
+                        arl_stream_t stream) {
+    if (!Y || !G || !rowptr || !col || !X || !gX || !tptr || !trow || !tperm || !dY || !workspace) return ARL_E_NULL;
+    if (!als_width(d)) return ARL_E_DIM;
+    if (target != ARL_ALS_TARGET_STORED && target != ARL_ALS_TARGET_RELAXED) return ARL_E_ARG;
+    if (n <= 0 || n_rows <= 0 || nnz <= 0 || !(alpha >= 0.0) || !(lambda >= 0.0)) return ARL_E_ARG;
+    if (!als_rows_ok(n) || !als_rows_ok(n_rows) || nnz > 0x7fffffffll) return ARL_E_RANGE;
+    if (((uintptr_t)Y | (uintptr_t)G | (uintptr_t)X | (uintptr_t)gX | (uintptr_t)dY | (uintptr_t)workspace) & 15) return ARL_E_ARG;
+    split_len = als_split(split_len);
+    col_split_len = alsgrad_col_split(col_split_len);
+    if (split_len > 0x7fffffffll) split_len = 0x7fffffffll;
+    if (col_split_len > 0x7fffffffll) col_split_len = 0x7fffffffll;
+    if (als_max_pieces(n_rows, nnz, split_len) > 0x7fffffffll || als_max_pieces(n, nnz, col_split_len) > 0x7fffffffll) return ARL_E_RANGE;
+    const double b0 = target == ARL_ALS_TARGET_STORED ? 1.0 : 0.0, b1 = target == ARL_ALS_TARGET_STORED ? alpha : 1.0 + alpha;
+    hipStream_t st = (hipStream_t)stream;
+#define ALS_RUN(DD) return alsgrad_run<DD>(Y, n, G, rowptr, col, val, n_rows, nnz, X, gX, tptr, trow, tperm, alpha, lambda, b0, b1, split_len, col_split_len, dY, dval, (char *)workspace, st)
     if (d == 16) ALS_RUN(16);
     if (d == 32) ALS_RUN(32);
     if (d == 64) ALS_RUN(64);

@@ -1964,3 +1964,7 @@ from .multinomial import (MULTINOMIAL_WIDTHS, MULTINOMIAL_MAX_ROWS, multinomial_
 # (module of its own: arlib_amd/als.py, with its poisoned-memory runs in tests/test_gpu_als_poison.py)
 from .als import (ALS_WIDTHS, ALS_MAX_ROWS, als_supported, gram, als_solve_rows_kernel, als_solve_rows_composed, als_solve_rows,  # noqa: E402,F401
                   als_objective)
+
+# ================================================================================================ the differentiable ALS row solve (csrc/arl_als.hip)
+# (module of its own: arlib_amd/alsgrad.py, with its poisoned-memory runs in tests/test_gpu_alsgrad_poison.py)
+from .alsgrad import (ALSGRAD_TARGETS, als_solve_rows_target, als_adjoint_kernel, als_adjoint_composed, als_adjoint, als_solve)  # noqa: E402,F401

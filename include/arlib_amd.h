@@ -786,6 +786,34 @@ int64_t arl_als_objective_workspace_bytes(int64_t n_rows, int64_t n, int64_t d);
 int arl_als_objective_f64(const float *X, int64_t n_rows, const float *Y, int64_t n, int64_t d, const double *G, const int32_t *rowptr, const int32_t *col,
                           const float *val, double alpha, double lambda, double *out, void *workspace, arl_stream_t stream);
 
+/* The row solve under a target rule, and its adjoint (csrc/arl_als.hip; the operator an attack needs to differentiate through ALS sweeps, as in Tang,
+ * Wen, Wang, RecSys'20).  b_r = sum_{i in P_r} beta(w_ri) y_i with
+ *   ARL_ALS_TARGET_STORED : beta(w) = 1 + alpha w      (arl_als_solve_rows_f32: the same launches, the same bits)
+ *   ARL_ALS_TARGET_RELAXED: beta(w) = (1 + alpha) w    (the same double at w = 1; an entry of weight 0 contributes nothing, as if it were absent)
+ * solve_rows_target: arl_als_solve_rows_f32 with the rule selectable; arguments, limits and workspace as there.
+ * adjoint: given X [n_rows, d] = the solved rows (all of them, in row order) and gX [n_rows, d] = dL/dX, with z_r = A_r^-1 g_r, s = x_r . y_i,
+ *   t = z_r . y_i and C = sum_r z_r x_r^T:
+ *     dval[e] = t (beta'(w) - alpha s)                                                        beta' = alpha | 1 + alpha       (dval NULL: skipped)
+ *     dY[i]   = sum_{r with i} [ (beta(w_ri) - alpha w_ri s) z_r - alpha w_ri t x_r ] - y_i (C + C^T)      (the last term: the path through G = Y^T Y)
+ *   A_r is rebuilt and factorised as in the forward (exact fp32 MFMA tiles, double from there on) with g_r travelling where b_r travels; s and t are
+ *   double dots; C is summed in double over the fixed spans of the Gram kernel; dY[i] runs over the entries of column i in the transposed order
+ *   (tptr [n + 1], trow [nnz] the row ids, tperm [nnz] the entries' positions in the by-row arrays), in double, a column longer than col_split_len
+ *   (<= 0: arl_als_default_col_split_len) cut into pieces added in piece order.  A row without entries has z = 0 and contributes nothing whatever gX
+ *   holds.  nnz >= 1.  No atomics, one writer per word, fixed orders: bit-identical from run to run (for given split lengths); no n_rows x d x d
+ *   stack.  workspace: arl_als_adjoint_workspace_bytes (0 outside the limits), no initialisation needed.  Limits and error codes as above. */
+#define ARL_ALS_TARGET_STORED 0
+#define ARL_ALS_TARGET_RELAXED 1
+int64_t arl_als_solve_rows_target_workspace_bytes(int64_t n_solve, int64_t nnz_listed, int64_t d, int64_t split_len);
+int arl_als_solve_rows_target_f32(const float *Y, int64_t n, int64_t d, const double *G, const int32_t *rowptr, const int32_t *col, const float *val,
+                                  int64_t n_rows, const int32_t *rows, int64_t n_solve, int64_t nnz_listed, double alpha, double lambda, int32_t target,
+                                  int64_t split_len, float *X, void *workspace, arl_stream_t stream);
+int64_t arl_als_default_col_split_len(void);
+int64_t arl_als_adjoint_workspace_bytes(int64_t n, int64_t n_rows, int64_t nnz, int64_t d, int64_t split_len, int64_t col_split_len);
+int arl_als_adjoint_f32(const float *Y, int64_t n, int64_t d, const double *G, const int32_t *rowptr, const int32_t *col, const float *val, int64_t n_rows,
+                        int64_t nnz, const float *X, const float *gX, const int32_t *tptr, const int32_t *trow, const int32_t *tperm, double alpha,
+                        double lambda, int32_t target, int64_t split_len, int64_t col_split_len, float *dY, float *dval, void *workspace,
+                        arl_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Lloyd's k-means for NCL's prototypes (csrc/arl_kmeans.hip).  Replaces recommender/NCL.py:52-73 (e_step / run_kmeans: sklearn's KMeans on
  * host copies of the tables; the commented faiss.Kmeans(gpu=True) of :61-66 is what the authors meant).  X [N, d] points, C [k, d]
