@@ -29,6 +29,11 @@ class arl_blocked(C.Structure):
                 ('partial', C.c_void_p), ('waves_per_group', C.c_int64)]
 
 
+class arl_blocked_hop(C.Structure):
+    _fields_ = [('n_split', C.c_int64), ('split_row', C.c_void_p), ('split_first', C.c_void_p), ('split_count', C.c_void_p), ('partial', C.c_void_p),
+                ('stream_len', C.POINTER(C.c_int64))]
+
+
 _vp, _i64, _i32, _f = C.c_void_p, C.c_int64, C.c_int32, C.c_float
 _SIGS = {
     'arl_abi_version': (C.c_int, []),
@@ -50,6 +55,12 @@ _SIGS = {
     'arl_spmm_blocked_rscale_f32': (C.c_int, [C.POINTER(arl_blocked), _vp, _i64, _vp, _f, _f, _vp, _vp, _vp]),
     'arl_spmm_blocked_layersum_f32': (C.c_int, [C.POINTER(arl_blocked), _vp, _i64, _vp, _vp, _vp, _vp]),
     'arl_spmm_blocked_adam_f32': (C.c_int, [C.POINTER(arl_blocked), _vp, _i64, _f, _f, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i64, _vp]),
+    'arl_spmm_blocked_sets_f32': (C.c_int, [C.POINTER(arl_blocked), _i64, _i64, C.POINTER(arl_blocked_hop), _vp, _i64, _f, _f, _vp, _vp, _vp, _vp]),
+    'arl_spmm_blocked_flagged_sets_f32': (C.c_int, [C.POINTER(arl_blocked), _i64, _i64, C.POINTER(arl_blocked_hop), _vp, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp]),
+    'arl_spmm_blocked_rscale_sets_f32': (C.c_int, [C.POINTER(arl_blocked), _i64, _i64, C.POINTER(arl_blocked_hop), _vp, _i64, _vp, _f, _f, _vp, _vp, _vp]),
+    'arl_spmm_blocked_layersum_sets_f32': (C.c_int, [C.POINTER(arl_blocked), _i64, _i64, C.POINTER(arl_blocked_hop), _vp, _i64, _vp, _vp, _vp, _vp]),
+    'arl_spmm_blocked_adam_sets_f32': (C.c_int, [C.POINTER(arl_blocked), _i64, _i64, C.POINTER(arl_blocked_hop), _vp, _i64, _f, _f, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f,
+                                                 _i64, _vp]),
     'arl_lpt_deal': (C.c_int, [_i64, _vp, _i64, _i64, _vp, _vp]),
     'arl_syn_v1_pairs': (_i64, [_i64, _i64, C.c_double, C.c_uint64, C.c_double, _i64, _i64, _vp, _i64]),
     'arl_graph_digest': (C.c_uint64, [_vp, _i64]),

@@ -16,6 +16,8 @@
 #include "arl_stream.h"
 #include "arl_ordered.h"
 #include <type_traits>
+#include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -779,12 +781,38 @@ template <int MODE, bool MASKED> constexpr int kEpiGroup = MODE == EPI_ADAM ? 2 
 // -0), so the result has the bits of the unmasked kernel on the same operand; an all-clear batch costs its record load and the ballot.
 constexpr int kMaskedUnr = 8;
 
-template <int RPW, int MODE, int UNR, int CPL, int LD = 64 * CPL, bool MASKED = false>       // LD: row stride (floats) of the operand and of every table the epilogue touches
-__global__ __launch_bounds__(kBlock) void spmm_blocked64_kernel(BlockedDev P, const float *__restrict__ X, Epi ep) {
+// The masked hop of a whole plan in ONE grid (PLAN = BlockedSetsDev): the row sets' launches are independent (same operand, same bitmap,
+// disjoint output rows) and each is bound by its waves' chain record batch -> bitmap word -> ballot -> gather, not by bandwidth, so side by
+// side they cost about the longer of the two instead of their sum.  The grid is the concatenation of the sets' workgroups in the order the
+// host chose (longest record stream per wave first, so the long waves start first), all of one shape: the smallest waves-per-group of the
+// sets (cfg2: 1; measured against every set keeping its own shape in a block of the largest, profiles/hop_sets.md).  The set is picked with
+// wave-uniform selects between the by-value structs (no indexed copy of them); from there on a wave runs what it runs in a launch of its
+// set alone.
+constexpr int kMaxMergedSets = 4;
+struct BlockedSetsDev {
+    int n;
+    int block_end[kMaxMergedSets];      // one past set i's last workgroup in the merged grid
+    BlockedDev s[kMaxMergedSets];
+};
+
+template <int RPW, int MODE, int UNR, int CPL, int LD = 64 * CPL, bool MASKED = false, typename PLAN = BlockedDev>       // LD: row stride (floats) of the operand and of every table the epilogue touches
+__global__ __launch_bounds__(kBlock) void spmm_blocked64_kernel(PLAN plan, const float *__restrict__ X, Epi ep) {
     static_assert(RPW == 16 || RPW == 32, "accumulators are 32-register vectors");
     static_assert(CPL == 1 || CPL == 2, "d = 64 (one column per lane) or d = 128 (two adjacent columns per lane)");
     const int lane = threadIdx.x & 63;
-    const int w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    BlockedDev P;
+    int w;
+    if constexpr (std::is_same<PLAN, BlockedSetsDev>::value) {
+        P = plan.s[0];
+        int b0 = 0;
+#pragma unroll
+        for (int i = 1; i < kMaxMergedSets; ++i)
+            if (i < plan.n && (int)blockIdx.x >= plan.block_end[i - 1]) { P = plan.s[i]; b0 = plan.block_end[i - 1]; }
+        w = ((int)blockIdx.x - b0) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    } else {
+        P = plan;
+        w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    }
     if (w >= P.n_waves) return;
     f32x32v acc[CPL];
 #pragma unroll
@@ -934,62 +962,149 @@ static int launch_blocked64(dim3 grid, dim3 block, hipStream_t st, const Blocked
     return ARL_OK;
 }
 
-template <int MODE>
-int launch_spmm_blocked(const arl_blocked *P, const float *X, int64_t d, const Epi &ep, hipStream_t st, const uint32_t *xbits = nullptr) {
-    if (!P || !X) return ARL_E_NULL;
-    if (d != 64 && d != 128) return ARL_E_DIM;
+// the argument checks of one row set; ARL_OK for an empty set too (n_waves == 0: nothing is launched, nothing else is looked at)
+static int blocked_set_check(const arl_blocked *P) {
     if (P->n_waves < 0 || P->n_waves > 0x7fffffffll / 64) return ARL_E_RANGE;
     if (P->rows_per_wave != 16 && P->rows_per_wave != 32) return ARL_E_ARG;
     if (P->n_waves == 0) return ARL_OK;
     if (!P->wave_ptr || !P->wave_rows || !P->rec_col || !P->rec_val) return ARL_E_NULL;
     if (P->n_split < 0 || P->n_split > 0x7fffffffll) return ARL_E_RANGE;
     if (P->n_split > 0 && (!P->split_row || !P->split_first || !P->split_count || !P->partial)) return ARL_E_NULL;
-    BlockedDev D = {(int)P->n_waves, P->wave_ptr, P->wave_rows, P->rec_col, P->rec_val, P->partial, xbits};
     const int64_t wpg = P->waves_per_group ? P->waves_per_group : kWavesPerBlock;
     if (wpg != 1 && wpg != 2 && wpg != 4) return ARL_E_ARG;
-    const dim3 grid((unsigned)((P->n_waves + wpg - 1) / wpg)), block((unsigned)(wpg * kWave));
     if (P->loads_in_flight != 16 && P->loads_in_flight != 32) return ARL_E_ARG;
-    int rc;
-    if (d == 128) {
-        // d = 128 as two d = 64 passes over the column halves of the 128-wide tables (row stride 128): the one-column-per-lane kernel moves
-        // 12.2 TB/s of gathered rows, the two-column one 10.3 (fewer rows in flight at 118 registers) -- the second pass over the 8-B
-        // record stream costs less than that buys.  The split rows' pieces of a half use the front of `partial` and are combined before
-        // the next half overwrites them (stream order).
-        for (int half = 0; half < 2; ++half) {
-            Epi e2 = ep;
-            e2.ld = 128;
-            const int off = 64 * half;
-            if (e2.Z) e2.Z += off;
-            if (e2.Y) e2.Y += off;
-            if (e2.S_in) e2.S_in += off;
-            if (e2.S) e2.S += off;
-            if (e2.P) e2.P += off;
-            if (e2.M) e2.M += off;
-            if (e2.V) e2.V += off;
-            if (P->rows_per_wave == 16) rc = launch_blocked64<16, MODE, 16, 1, 128>(grid, block, st, D, X + off, e2);
-            else if (P->loads_in_flight == 16) rc = launch_blocked64<32, MODE, 16, 1, 128>(grid, block, st, D, X + off, e2);
-            else rc = launch_blocked64<32, MODE, 32, 1, 128>(grid, block, st, D, X + off, e2);
-            if (rc != ARL_OK) return rc;
-            if (P->n_split > 0) {
-                CsrDev C = {};
-                C.n_long = (int)P->n_split; C.long_row = P->split_row; C.long_first = P->split_first; C.long_count = P->split_count; C.partial = P->partial;
-                const unsigned grid_long = (unsigned)((C.n_long + kWavesPerBlock - 1) / kWavesPerBlock);
-                hipLaunchKernelGGL((spmm_long_rows_kernel<16, MODE>), dim3(grid_long), dim3(kBlock), 0, st, C, 64, e2);
-                ARL_LAUNCH_CHECK();
-            }
-        }
-        return ARL_OK;
+    return ARL_OK;
+}
+
+static BlockedDev blocked_dev(const arl_blocked *P, const uint32_t *xbits) {
+    return {(int)P->n_waves, P->wave_ptr, P->wave_rows, P->rec_col, P->rec_val, P->partial, xbits};
+}
+
+// one (checked, non-empty) row set in a launch of its own, on 64 columns of tables whose row stride is LD
+template <int MODE, int LD>
+static int launch_blocked_set(const arl_blocked *P, const float *X, const Epi &ep, hipStream_t st, const uint32_t *xbits) {
+    const BlockedDev D = blocked_dev(P, xbits);
+    const int64_t wpg = P->waves_per_group ? P->waves_per_group : kWavesPerBlock;
+    const dim3 grid((unsigned)((P->n_waves + wpg - 1) / wpg)), block((unsigned)(wpg * kWave));
+    if (P->rows_per_wave == 16) return launch_blocked64<16, MODE, 16, 1, LD>(grid, block, st, D, X, ep);
+    if (P->loads_in_flight == 16) return launch_blocked64<32, MODE, 16, 1, LD>(grid, block, st, D, X, ep);
+    return launch_blocked64<32, MODE, 32, 1, LD>(grid, block, st, D, X, ep);
+}
+
+// split rows: add the pieces in piece order and run the epilogue (64 columns; ep.ld is the tables' row stride when it is not 64)
+template <int MODE>
+static int launch_split_combine(int64_t n_split, const int32_t *row, const int32_t *first, const int32_t *count, float *partial, const Epi &ep, hipStream_t st) {
+    if (n_split <= 0) return ARL_OK;
+    CsrDev C = {};
+    C.n_long = (int)n_split; C.long_row = row; C.long_first = first; C.long_count = count; C.partial = partial;
+    const unsigned grid_long = (unsigned)((C.n_long + kWavesPerBlock - 1) / kWavesPerBlock);
+    hipLaunchKernelGGL((spmm_long_rows_kernel<16, MODE>), dim3(grid_long), dim3(kBlock), 0, st, C, 64, ep);
+    ARL_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
+// d = 128 as two d = 64 passes over the column halves of the 128-wide tables (row stride 128): the one-column-per-lane kernel moves
+// 12.2 TB/s of gathered rows, the two-column one 10.3 (fewer rows in flight at 118 registers) -- the second pass over the 8-B
+// record stream costs less than that buys.  The split rows' pieces of a half use `partial` and are combined before the next half
+// overwrites them (stream order).
+static Epi epi_half(const Epi &ep, int half) {
+    Epi e2 = ep;
+    e2.ld = 128;
+    const int off = 64 * half;
+    if (e2.Z) e2.Z += off;
+    if (e2.Y) e2.Y += off;
+    if (e2.S_in) e2.S_in += off;
+    if (e2.S) e2.S += off;
+    if (e2.P) e2.P += off;
+    if (e2.M) e2.M += off;
+    if (e2.V) e2.V += off;
+    return e2;
+}
+
+template <int MODE>
+int launch_spmm_blocked(const arl_blocked *P, const float *X, int64_t d, const Epi &ep, hipStream_t st, const uint32_t *xbits = nullptr) {
+    if (!P || !X) return ARL_E_NULL;
+    if (d != 64 && d != 128) return ARL_E_DIM;
+    if (int rc = blocked_set_check(P)) return rc;
+    if (P->n_waves == 0) return ARL_OK;
+    for (int half = 0; half < (d == 128 ? 2 : 1); ++half) {
+        const Epi e2 = d == 128 ? epi_half(ep, half) : ep;
+        int rc = d == 128 ? launch_blocked_set<MODE, 128>(P, X + 64 * half, e2, st, xbits) : launch_blocked_set<MODE, 64>(P, X, e2, st, xbits);
+        if (rc != ARL_OK) return rc;
+        rc = launch_split_combine<MODE>(P->n_split, P->split_row, P->split_first, P->split_count, P->partial, e2, st);
+        if (rc != ARL_OK) return rc;
     }
-    if (P->rows_per_wave == 16) rc = launch_blocked64<16, MODE, 16, 1, 64>(grid, block, st, D, X, ep);
-    else if (P->loads_in_flight == 16) rc = launch_blocked64<32, MODE, 16, 1, 64>(grid, block, st, D, X, ep);
-    else rc = launch_blocked64<32, MODE, 32, 1, 64>(grid, block, st, D, X, ep);
-    if (rc != ARL_OK) return rc;
-    if (P->n_split > 0) {                                // split rows: add the pieces in piece order and run the epilogue
-        CsrDev C = {};
-        C.n_long = (int)P->n_split; C.long_row = P->split_row; C.long_first = P->split_first; C.long_count = P->split_count; C.partial = P->partial;
-        const unsigned grid_long = (unsigned)((C.n_long + kWavesPerBlock - 1) / kWavesPerBlock);
-        hipLaunchKernelGGL((spmm_long_rows_kernel<16, MODE>), dim3(grid_long), dim3(kBlock), 0, st, C, 64, ep);
-        ARL_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
+// the masked hop of sets[order[0 .. m)] (checked, non-empty, one rows_per_wave) as one grid
+template <int LD>
+static int launch_masked_sets(const arl_blocked *sets, const int *order, int m, const float *X, const Epi &ep, hipStream_t st, const uint32_t *xbits) {
+    BlockedSetsDev S = {};
+    S.n = m;
+    int64_t blocks = 0, wpg = kWavesPerBlock;
+    for (int i = 0; i < m; ++i) wpg = std::min<int64_t>(wpg, sets[order[i]].waves_per_group ? sets[order[i]].waves_per_group : kWavesPerBlock);
+    for (int i = 0; i < m; ++i) {
+        const arl_blocked *P = sets + order[i];
+        blocks += (P->n_waves + wpg - 1) / wpg;
+        if (blocks > 0x7fffffffll) return ARL_E_RANGE;
+        S.block_end[i] = (int)blocks; S.s[i] = blocked_dev(P, xbits);
+    }
+    for (int i = m; i < kMaxMergedSets; ++i) { S.block_end[i] = (int)blocks; S.s[i] = S.s[0]; }
+    const dim3 grid((unsigned)blocks), block((unsigned)(wpg * kWave));
+    if (sets[order[0]].rows_per_wave == 16) hipLaunchKernelGGL((spmm_blocked64_kernel<16, EPI_AXPBY, 16, 1, LD, true, BlockedSetsDev>), grid, block, 0, st, S, X, ep);
+    else hipLaunchKernelGGL((spmm_blocked64_kernel<32, EPI_AXPBY, 16, 1, LD, true, BlockedSetsDev>), grid, block, 0, st, S, X, ep);
+    ARL_LAUNCH_CHECK();
+    return ARL_OK;
+}
+
+// One hop over the row sets [first, n_sets) of a plan: the sets' launches, then ONE combine for the split rows of all of them (`hop` holds
+// their tables back to back, split_first counting pieces of the one workspace that the sets' `partial` areas are slices of).  Every wave
+// runs the records it runs in the per-set calls, in the same order, and a split row adds the same pieces in the same order: same bits.
+// The masked hop runs all sets in one grid where they agree on rows_per_wave (and are at most kMaxMergedSets).
+template <int MODE>
+int launch_spmm_blocked_sets(const arl_blocked *sets, int64_t n_sets, int64_t first, const arl_blocked_hop *hop, const float *X, int64_t d, const Epi &ep,
+                             hipStream_t st, const uint32_t *xbits = nullptr) {
+    if (!X || (n_sets > 0 && !sets)) return ARL_E_NULL;
+    if (d != 64 && d != 128) return ARL_E_DIM;
+    if (n_sets < 0 || n_sets > 0x7fffffffll || first < 0 || first > n_sets) return ARL_E_RANGE;
+    if (xbits && MODE != EPI_AXPBY) return ARL_E_ARG;
+    int64_t skipped = 0, n_split = 0;                    // split rows of the sets before `first`, and of the sets that run
+    std::vector<int> run;                                // the non-empty sets that run
+    bool one_rpw = true;
+    for (int64_t k = 0; k < n_sets; ++k) {
+        if (int rc = blocked_set_check(sets + k)) return rc;
+        if (sets[k].n_split < 0 || sets[k].n_split > 0x7fffffffll) return ARL_E_RANGE;
+        if (k < first) { skipped += sets[k].n_split; continue; }
+        n_split += sets[k].n_split;
+        if (sets[k].n_waves == 0) { if (sets[k].n_split) return ARL_E_ARG; continue; }
+        if (!run.empty() && sets[k].rows_per_wave != sets[run[0]].rows_per_wave) one_rpw = false;
+        run.push_back((int)k);
+    }
+    if (run.empty()) return ARL_OK;
+    if (n_split > 0) {
+        if (!hop || !hop->split_row || !hop->split_first || !hop->split_count || !hop->partial) return ARL_E_NULL;
+        if (skipped + n_split > hop->n_split) return ARL_E_ARG;
+    }
+    const int m = (int)run.size();
+    const bool merged = xbits && m > 1 && m <= kMaxMergedSets && one_rpw;
+    if (merged && hop && hop->stream_len)                // longest record stream per wave first
+        std::stable_sort(run.begin(), run.end(), [&](int a, int b) { return hop->stream_len[a] > hop->stream_len[b]; });
+    for (int half = 0; half < (d == 128 ? 2 : 1); ++half) {
+        const Epi e2 = d == 128 ? epi_half(ep, half) : ep;
+        const float *Xh = X + 64 * half;
+        int rc = ARL_OK;
+        if (merged) {
+            if constexpr (MODE == EPI_AXPBY) rc = d == 128 ? launch_masked_sets<128>(sets, run.data(), m, Xh, e2, st, xbits) : launch_masked_sets<64>(sets, run.data(), m, Xh, e2, st, xbits);
+        } else {
+            for (int i = 0; i < m && rc == ARL_OK; ++i)
+                rc = d == 128 ? launch_blocked_set<MODE, 128>(sets + run[i], Xh, e2, st, xbits) : launch_blocked_set<MODE, 64>(sets + run[i], Xh, e2, st, xbits);
+        }
+        if (rc != ARL_OK) return rc;
+        if (n_split > 0) {
+            rc = launch_split_combine<MODE>(n_split, hop->split_row + skipped, hop->split_first + skipped, hop->split_count + skipped, hop->partial, e2, st);
+            if (rc != ARL_OK) return rc;
+        }
     }
     return ARL_OK;
 }
@@ -4384,6 +4499,45 @@ int arl_spmm_blocked_adam_f32(const arl_blocked *P, const float *X, int64_t d, f
     Epi ep;
     if (int rc = epi_adam(ep, X, alpha, beta, Z, zflags, Pm, M, V, lr, beta1, beta2, eps, step)) return rc;
     return launch_spmm_blocked<EPI_ADAM>(P, X, d, ep, (hipStream_t)stream);
+}
+
+// ---- the same five hops over the row sets [first, n_sets) of a whole plan (launch_spmm_blocked_sets)
+int arl_spmm_blocked_sets_f32(const arl_blocked *sets, int64_t n_sets, int64_t first, const arl_blocked_hop *hop, const float *X, int64_t d, float alpha,
+                              float beta, const float *Z, const uint8_t *zflags, float *Y, arl_stream_t stream) {
+    Epi ep;
+    if (int rc = epi_axpby(ep, X, alpha, beta, Z, zflags, Y, nullptr)) return rc;
+    return launch_spmm_blocked_sets<EPI_AXPBY>(sets, n_sets, first, hop, X, d, ep, (hipStream_t)stream);
+}
+
+int arl_spmm_blocked_flagged_sets_f32(const arl_blocked *sets, int64_t n_sets, int64_t first, const arl_blocked_hop *hop, const float *X, int64_t d,
+                                      const uint32_t *xbits, float alpha, float beta, const float *Z, const uint8_t *zflags, float *Y, arl_stream_t stream) {
+    if (!xbits) return ARL_E_NULL;
+    Epi ep;
+    if (int rc = epi_axpby(ep, X, alpha, beta, Z, zflags, Y, nullptr)) return rc;
+    return launch_spmm_blocked_sets<EPI_AXPBY>(sets, n_sets, first, hop, X, d, ep, (hipStream_t)stream, xbits);
+}
+
+int arl_spmm_blocked_rscale_sets_f32(const arl_blocked *sets, int64_t n_sets, int64_t first, const arl_blocked_hop *hop, const float *X, int64_t d,
+                                     const float *row_scale, float alpha, float beta, const float *Z, float *Y, arl_stream_t stream) {
+    if (!row_scale) return ARL_E_NULL;
+    Epi ep;
+    if (int rc = epi_axpby(ep, X, alpha, beta, Z, nullptr, Y, row_scale)) return rc;
+    return launch_spmm_blocked_sets<EPI_AXPBY>(sets, n_sets, first, hop, X, d, ep, (hipStream_t)stream);
+}
+
+int arl_spmm_blocked_layersum_sets_f32(const arl_blocked *sets, int64_t n_sets, int64_t first, const arl_blocked_hop *hop, const float *X, int64_t d,
+                                       const float *S_in, float *S, float *Y, arl_stream_t stream) {
+    Epi ep;
+    if (int rc = epi_layersum(ep, X, S_in, S, Y)) return rc;
+    return launch_spmm_blocked_sets<EPI_LAYERSUM>(sets, n_sets, first, hop, X, d, ep, (hipStream_t)stream);
+}
+
+int arl_spmm_blocked_adam_sets_f32(const arl_blocked *sets, int64_t n_sets, int64_t first, const arl_blocked_hop *hop, const float *X, int64_t d, float alpha,
+                                   float beta, const float *Z, const uint8_t *zflags, float *Pm, float *M, float *V, float lr, float beta1, float beta2,
+                                   float eps, int64_t step, arl_stream_t stream) {
+    Epi ep;
+    if (int rc = epi_adam(ep, X, alpha, beta, Z, zflags, Pm, M, V, lr, beta1, beta2, eps, step)) return rc;
+    return launch_spmm_blocked_sets<EPI_ADAM>(sets, n_sets, first, hop, X, d, ep, (hipStream_t)stream);
 }
 
 int arl_spmm_csr_flagged_f32(const arl_csr *A, const float *X, int64_t d, const uint32_t *xbits, float alpha, float beta, const float *Z,

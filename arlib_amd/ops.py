@@ -362,10 +362,30 @@ class BlockedPlan:
         hub_rows = torch.cat(hub_rows) if hub_rows else torch.zeros(0, dtype=torch.int64, device=dev)
         self.n_hub = int(hub_rows.numel())
         self._hub_rows = hub_rows
+        self._join_splits(dev)
         self._bind(A)
+
+    def _join_splits(self, dev):
+        """The plan's split rows as one table (arl_blocked_hop): the sets' split_row / split_first / split_count back to back, split_first counting
+        pieces of ONE workspace, of which a set's own `partial` is the slice from its first piece on (64 floats per piece at either width: d = 128
+        runs as two 64-column passes).  A hop over the whole plan then combines the split rows of every set in one launch; a set launched alone
+        still finds its own tables and its slice.  Built once per pattern: with_values and the patched plans share it.  Every set keeps a
+        reference to the joined tables and its offset in them (hop_structs reads them from the sets it is asked to run)."""
+        off, soff, tabs = 0, 0, []
+        for st in self.sets:
+            st['piece_off'], st['split_off'] = off, soff
+            if st['n_split']:
+                tabs.append((st['split_row'], st['split_first'] + off, st['split_count']))
+            off += st['n_pieces']; soff += st['n_split']
+        partial = torch.empty(max(off, 1) * 64, dtype=torch.float32, device=dev)
+        joined = {'partial': partial, 'tables': tuple(torch.cat(t).contiguous() for t in zip(*tabs)) if tabs else None}
+        for st in self.sets:
+            st['joined'] = joined
+            st['partial'] = partial[st['piece_off'] * 64:(st['piece_off'] + st['n_pieces']) * 64]
 
     def _bind(self, A, hub=None):
         self.structs = []
+        self._hop_c = None
         for st in self.sets:
             if A.nnz:
                 st['rec_val'] = A.val[st['rec_src']]
@@ -379,14 +399,33 @@ class BlockedPlan:
             self.hub = A.chunks_only(self._hub_rows) if self.n_hub else None
 
     def struct(self, k, d):
-        """ctypes image of row set k for an operand of width d (the split rows' [n_pieces, d] workspace is sized here)."""
+        """ctypes image of row set k for an operand of width d."""
         st = self.sets[k]
         n_sp = st.get('n_split', 0)
-        if n_sp and (st.get('partial') is None or st['partial'].numel() < st['n_pieces'] * d):
-            st['partial'] = torch.empty(st['n_pieces'] * d, dtype=torch.float32, device=st['rec_col'].device)
         return _lib.arl_blocked(st['n_waves'], self.rpw, st['unroll'], st['wave_ptr'].data_ptr(), st['wave_rows'].data_ptr(), st['rec_col'].data_ptr(),
                                 st['rec_val'].data_ptr(), n_sp, st['split_row'].data_ptr() if n_sp else None, st['split_first'].data_ptr() if n_sp else None,
                                 st['split_count'].data_ptr() if n_sp else None, st['partial'].data_ptr() if n_sp else None, int(st['wpg']))
+
+    def hop_structs(self, d):
+        """ctypes image of the plan's sets for the arl_spmm_blocked_*_sets_f32 calls: (array of the sets' structs, their number, arl_blocked_hop), or
+        None when the sets are not a run of one plan's sets in order (their split rows are then not one stretch of the joined tables)."""
+        sets = self.sets
+        key = tuple(id(st) for st in sets)
+        if self._hop_c is None or self._hop_c[0] != key:
+            n = len(sets)
+            j = sets[0].get('joined') if n else None
+            ok = all(st.get('joined') is j and (i == 0 or st['split_off'] == sets[i - 1]['split_off'] + sets[i - 1]['n_split']) for i, st in enumerate(sets))
+            if n == 0 or j is None or not ok:
+                self._hop_c = (key, None, None, tuple(sets))
+            else:
+                arr = (_lib.arl_blocked * n)(*[self.struct(k, d) for k in range(n)])
+                slen = (C.c_int64 * n)(*[st['rec_col'].numel() // max(1, st['n_waves']) for st in sets])
+                n_sp, o = sum(st['n_split'] for st in sets), 4 * sets[0]['split_off']
+                tb = j['tables'] if n_sp else None
+                hop = _lib.arl_blocked_hop(n_sp, tb[0].data_ptr() + o if tb else None, tb[1].data_ptr() + o if tb else None, tb[2].data_ptr() + o if tb else None,
+                                           j['partial'].data_ptr(), slen)
+                self._hop_c = (key, (arr, n, hop), slen, tuple(sets))      # the ids stay theirs while the sets are held
+        return self._hop_c[1]
 
     def with_values(self, A):
         """The same plan over a graph with the same pattern and new edge values."""
@@ -423,15 +462,27 @@ def auto_blocked(graph, d, split=None, force=False, rows_per_wave=32, small_laun
     return graph
 
 
-def _spmm_dispatch(A, d, blocked_call, csr_call, tag, rows_from=0):
+HOP_SETS = True      # a plan that holds every row runs a hop as ONE native call over its row sets (False: one call per set, the same bits)
+
+
+def _spmm_dispatch(A, d, blocked_call, csr_call, tag, rows_from=0, sets_call=None):
     """Run one full-table SpMM: through the blocked plan (+ its hub rows through the chunked CSR kernel) when the graph has one
     and d = 64 or 128, else through the CSR kernel.  The callables take the ctypes struct pointer.  rows_from > 0: the caller does not
     read output rows below it -- launches of the plan that only produce such rows are skipped (the CSR schedule ignores the hint).
+    A plan that holds every row of the graph (no hub view: the default, split_hubs) goes through `sets_call(sets, n_sets, first, hop)`, one
+    native call for the whole hop: one combine for the split rows of all sets and, masked, one grid for all sets.  A plan that leaves hub
+    rows to the CSR kernel keeps one call per set and the CSR call after them.
     The launches are bracketed with EVENT_HOOK under `tag` when a hook is installed."""
     tok = EVENT_HOOK.begin(tag) if EVENT_HOOK is not None else None
     bp = A.blocked
     if bp is None or d not in (64, 128):
         csr_call(C.byref(A._struct(d)))
+    elif HOP_SETS and sets_call is not None and bp.hub is None and bp.hop_structs(d) is not None:
+        first = 0
+        while first < len(bp.sets) and bp.sets[first]['hi'] <= rows_from:
+            first += 1
+        arr, n, hop = bp.hop_structs(d)
+        sets_call(arr, n, first, C.byref(hop))
     else:
         for k in range(len(bp.sets)):
             if bp.sets[k]['hi'] <= rows_from:
@@ -680,10 +731,12 @@ def spmm(A, X, alpha=1.0, beta=0.0, Z=None, out=None, row_scale=None, rows_from=
             raise ValueError('spmm: row_scale needs one entry per output row')
         _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_rscale_f32(p, _ptr(X), d, _ptr(row_scale), alpha, beta, zp, _ptr(Y), st), 'arl_spmm_blocked_rscale_f32'),
                        lambda p: check(L.arl_spmm_csr_rscale_f32(p, _ptr(X), d, _ptr(row_scale), alpha, beta, zp, _ptr(Y), st), 'arl_spmm_csr_rscale_f32'),
-                       'axpby', rows_from=rows_from)
+                       'axpby', rows_from=rows_from,
+                       sets_call=lambda *p: check(L.arl_spmm_blocked_rscale_sets_f32(*p, _ptr(X), d, _ptr(row_scale), alpha, beta, zp, _ptr(Y), st), 'arl_spmm_blocked_rscale_sets_f32'))
     else:
         _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_f32(p, _ptr(X), d, alpha, beta, zp, None, _ptr(Y), st), 'arl_spmm_blocked_f32'),
-                       lambda p: check(L.arl_spmm_csr_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(Y), st), 'arl_spmm_csr_f32'), 'axpby', rows_from=rows_from)
+                       lambda p: check(L.arl_spmm_csr_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(Y), st), 'arl_spmm_csr_f32'), 'axpby', rows_from=rows_from,
+                       sets_call=lambda *p: check(L.arl_spmm_blocked_sets_f32(*p, _ptr(X), d, alpha, beta, zp, None, _ptr(Y), st), 'arl_spmm_blocked_sets_f32'))
     return Y
 
 
@@ -702,7 +755,8 @@ def spmm_layersum(A, X, S_in, S, Y=None):
         raise ValueError('spmm_layersum: S must not alias X')
     L, st = _lib.lib(), _stream()
     _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_layersum_f32(p, _ptr(X), d, _ptr(S_in), _ptr(S), _ptr(Y), st), 'arl_spmm_blocked_layersum_f32'),
-                   lambda p: check(L.arl_spmm_csr_layersum_f32(p, _ptr(X), d, _ptr(S_in), _ptr(S), _ptr(Y), st), 'arl_spmm_csr_layersum_f32'), 'layersum')
+                   lambda p: check(L.arl_spmm_csr_layersum_f32(p, _ptr(X), d, _ptr(S_in), _ptr(S), _ptr(Y), st), 'arl_spmm_csr_layersum_f32'), 'layersum',
+                   sets_call=lambda *p: check(L.arl_spmm_blocked_layersum_sets_f32(*p, _ptr(X), d, _ptr(S_in), _ptr(S), _ptr(Y), st), 'arl_spmm_blocked_layersum_sets_f32'))
     return S
 
 
@@ -715,7 +769,9 @@ def spmm_adam(A, X, alpha, beta, Z, P, M, V, lr, step, betas=(0.9, 0.999), eps=1
     _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_adam_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(zflags), _ptr(P), _ptr(M), _ptr(V), lr, betas[0],
                                                                      betas[1], eps, int(step), st), 'arl_spmm_blocked_adam_f32'),
                    lambda p: check(L.arl_spmm_csr_adam_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(zflags), _ptr(P), _ptr(M), _ptr(V), lr, betas[0], betas[1], eps,
-                                                           int(step), st), 'arl_spmm_csr_adam_f32'), 'adam')
+                                                           int(step), st), 'arl_spmm_csr_adam_f32'), 'adam',
+                   sets_call=lambda *p: check(L.arl_spmm_blocked_adam_sets_f32(*p, _ptr(X), d, alpha, beta, zp, _ptr(zflags), _ptr(P), _ptr(M), _ptr(V), lr, betas[0],
+                                                                               betas[1], eps, int(step), st), 'arl_spmm_blocked_adam_sets_f32'))
 
 
 def spmm_flagged(A, X, xflags=None, alpha=1.0, beta=0.0, Z=None, zflags=None, out=None):
@@ -732,9 +788,12 @@ def spmm_flagged(A, X, xflags=None, alpha=1.0, beta=0.0, Z=None, zflags=None, ou
     csr = lambda p: check(L.arl_spmm_csr_flagged_f32(p, _ptr(X), d, _ptr(xflags), alpha, beta, zp, _ptr(zflags), _ptr(Y), st), 'arl_spmm_csr_flagged_f32')
     if xflags is not None:              # the masked hop skips most edges: the blocked record stream with a bit test per record, else the row-per-group kernel
         _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_flagged_f32(p, _ptr(X), d, _ptr(xflags), alpha, beta, zp, _ptr(zflags), _ptr(Y), st),
-                                             'arl_spmm_blocked_flagged_f32'), csr, 'masked')
+                                             'arl_spmm_blocked_flagged_f32'), csr, 'masked',
+                       sets_call=lambda *p: check(L.arl_spmm_blocked_flagged_sets_f32(*p, _ptr(X), d, _ptr(xflags), alpha, beta, zp, _ptr(zflags), _ptr(Y), st),
+                                                  'arl_spmm_blocked_flagged_sets_f32'))
     else:
-        _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(zflags), _ptr(Y), st), 'arl_spmm_blocked_f32'), csr, 'axpby')
+        _spmm_dispatch(A, d, lambda p: check(L.arl_spmm_blocked_f32(p, _ptr(X), d, alpha, beta, zp, _ptr(zflags), _ptr(Y), st), 'arl_spmm_blocked_f32'), csr, 'axpby',
+                       sets_call=lambda *p: check(L.arl_spmm_blocked_sets_f32(*p, _ptr(X), d, alpha, beta, zp, _ptr(zflags), _ptr(Y), st), 'arl_spmm_blocked_sets_f32'))
     return Y
 
 

@@ -206,7 +206,7 @@ typedef struct arl_blocked {
     const int32_t *split_row;   /* [n_split] output row                                                    */
     const int32_t *split_first; /* [n_split] first piece                                                   */
     const int32_t *split_count; /* [n_split] number of pieces                                              */
-    float *partial;             /* [n_pieces][d] workspace                                                 */
+    float *partial;             /* [n_pieces][64] workspace (d = 128 runs as two 64-column passes)         */
     int64_t waves_per_group;    /* 1, 2 or 4 wavefronts per workgroup (0 = 4): the dispatcher balances workgroups, not waves, over
                                  * the CUs, so a launch of ~12 waves per CU is spread evenly only with small workgroups         */
 } arl_blocked;
@@ -228,6 +228,33 @@ int arl_spmm_blocked_layersum_f32(const arl_blocked *P, const float *X, int64_t 
 int arl_spmm_blocked_adam_f32(const arl_blocked *P, const float *X, int64_t d, float alpha, float beta, const float *Z,
                               const uint8_t *zflags, float *Pm, float *M, float *V, float lr, float beta1, float beta2,
                               float eps, int64_t step, arl_stream_t stream);
+/* The same hops over the row sets [first, n_sets) of a WHOLE plan in one call (first > 0: the caller does not read the output rows of the
+ * sets before it).  The sets' launches are followed by ONE combine of the split rows of all of them, and the masked hop runs the sets in one
+ * grid where they agree on rows_per_wave (at most 4 sets; else one launch per set as above).  Every wave runs the records it runs in the
+ * per-set calls and a split row adds the same pieces in the same order: the results have the bits of the per-set calls.
+ * arl_blocked_hop is what the plan holds for that: the sets' split_row / split_first / split_count tables back to back in set order, with
+ * split_first counting pieces of ONE workspace `partial` of which set k's own `partial` is the slice that starts at its first piece (64
+ * floats per piece), and stream_len (HOST array, [n_sets], may be NULL = array order): records per wave of every set -- the merged masked grid
+ * starts the set with the longest streams first.  hop may be NULL when no set that runs has split rows. */
+typedef struct arl_blocked_hop {
+    int64_t n_split;
+    const int32_t *split_row, *split_first, *split_count;
+    float *partial;
+    const int64_t *stream_len;
+} arl_blocked_hop;
+int arl_spmm_blocked_sets_f32(const arl_blocked *sets, int64_t n_sets, int64_t first, const arl_blocked_hop *hop, const float *X, int64_t d,
+                              float alpha, float beta, const float *Z, const uint8_t *zflags, float *Y, arl_stream_t stream);
+int arl_spmm_blocked_flagged_sets_f32(const arl_blocked *sets, int64_t n_sets, int64_t first, const arl_blocked_hop *hop, const float *X,
+                                      int64_t d, const uint32_t *xbits, float alpha, float beta, const float *Z, const uint8_t *zflags,
+                                      float *Y, arl_stream_t stream);
+int arl_spmm_blocked_rscale_sets_f32(const arl_blocked *sets, int64_t n_sets, int64_t first, const arl_blocked_hop *hop, const float *X,
+                                     int64_t d, const float *row_scale, float alpha, float beta, const float *Z, float *Y,
+                                     arl_stream_t stream);
+int arl_spmm_blocked_layersum_sets_f32(const arl_blocked *sets, int64_t n_sets, int64_t first, const arl_blocked_hop *hop, const float *X,
+                                       int64_t d, const float *S_in, float *S, float *Y, arl_stream_t stream);
+int arl_spmm_blocked_adam_sets_f32(const arl_blocked *sets, int64_t n_sets, int64_t first, const arl_blocked_hop *hop, const float *X,
+                                   int64_t d, float alpha, float beta, const float *Z, const uint8_t *zflags, float *Pm, float *M, float *V,
+                                   float lr, float beta1, float beta2, float eps, int64_t step, arl_stream_t stream);
 /* Host helper of the plan: rows sorted by edge count (descending) are dealt to the least loaded of n_bins waves with a free
  * slot (cap slots each); bin_out / slot_out receive the placement. */
 int arl_lpt_deal(int64_t n, const int32_t *weight_desc, int64_t n_bins, int64_t cap, int32_t *bin_out, int32_t *slot_out);
