@@ -189,6 +189,11 @@ _SIGS = {
     'arl_alignment_fwd_bwd_f32': (C.c_int, [_vp, _vp, _i64, _i64, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     'arl_corating_max_items': (_i64, []),
     'arl_corating_degree_i32': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    'arl_cooccur_max_k': (_i64, []),
+    'arl_cooccur_max_tile_rows': (_i64, []),
+    'arl_cooccur_default_tile_rows': (_i64, []),
+    'arl_cooccur_max_degree': (_i64, [_i32]),
+    'arl_cooccur_topk_i32': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i64, _vp, _i64, _vp, _vp, _vp]),
     'arl_comm_load': (C.c_int, [C.c_char_p]),
     'arl_comm_unique_id': (C.c_int, [_vp]),
     'arl_comm_init': (C.c_int, [_vp, _i64, _i64, _i64, C.POINTER(C.c_void_p)]),

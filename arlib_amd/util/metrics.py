@@ -242,3 +242,50 @@ class TargetRankMetric(object):
                 share = self._below(k).sum(0) / valid
             out.append(share if per_target else (float(np.nanmean(share)) if (valid > 0).any() else float('nan')))
         return out
+
+
+class DetectionMetric(object):
+    """How well per-user suspicion scores separate injected profiles from real ones (no reference counterpart).  scores [n]: higher = more
+    suspicious; fake_ids: the ids of the injected users (distinct, in [0, n)).  The ranking behind the @n figures is by descending score, ties
+    to the smaller id, so every figure is a function of the scores alone."""
+
+    def __init__(self, scores, fake_ids):
+        self.scores = np.asarray(scores, dtype=np.float64).ravel()
+        fake = np.asarray(fake_ids, dtype=np.int64).ravel()
+        n = len(self.scores)
+        if np.isnan(self.scores).any():
+            raise ValueError('DetectionMetric: NaN score')
+        if len(fake) and (fake.min() < 0 or fake.max() >= n or len(np.unique(fake)) != len(fake)):
+            raise ValueError('DetectionMetric: fake_ids must be distinct ids in [0, %d)' % n)
+        self.is_fake = np.zeros(n, bool)
+        self.is_fake[fake] = True
+        self._order = np.lexsort((np.arange(n), -self.scores))
+
+    def auc(self):
+        """Mann-Whitney: the share of (fake, real) pairs in which the fake user scores higher, a tied pair counting one half (average ranks).
+        Counted in integers and divided once; NaN without a fake or without a real user."""
+        pos, neg = np.sort(self.scores[self.is_fake]), np.sort(self.scores[~self.is_fake])
+        if len(pos) == 0 or len(neg) == 0:
+            return float('nan')
+        below = np.searchsorted(neg, pos, side='left').astype(np.int64)
+        tied = np.searchsorted(neg, pos, side='right').astype(np.int64) - below
+        return float(int(2 * below.sum() + tied.sum()) / (2 * len(pos) * len(neg)))
+
+    def _hits(self, n):
+        n = int(n)
+        if n < 1:
+            raise ValueError('DetectionMetric: n = %d, n >= 1 needed' % n)
+        return int(self.is_fake[self._order[:n]].sum()), min(n, len(self.scores))
+
+    def precision_at(self, n):
+        h, m = self._hits(n)
+        return h / m if m else float('nan')
+
+    def recall_at(self, n):
+        h, _ = self._hits(n)
+        f = int(self.is_fake.sum())
+        return h / f if f else float('nan')
+
+    def f1_at(self, n):
+        p, r = self.precision_at(n), self.recall_at(n)
+        return 2 * p * r / (p + r) if p + r > 0 else 0.0

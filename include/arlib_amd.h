@@ -931,6 +931,35 @@ int arl_corating_degree_i32(const int64_t *u_rowptr, const int32_t *u_col, const
                             int64_t n_items, const int32_t *order, int32_t *out, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact top-k co-occurrence neighbours of the rows of a sparse binary matrix (csrc/arl_cooccur.hip; no reference counterpart: the primitive
+ * under the profile detectors of arlib_amd/detect and, on the transposed input, under an item-kNN neighbour list).  X is n_rows x n_cols:
+ *   rowptr [n_rows + 1], col [nnz]    : X as CSR; every row a set, columns ascending and distinct within a row (the entry trusts this);
+ *   colptr [n_cols + 1], irow [nnz]   : the same matrix column-major, rows ascending within a column;
+ *   rows [n_queries] (optional)       : the query rows, any order, repeats allowed; NULL = query q is row q, and n_queries is then n_rows;
+ *   order [n_queries] (optional)      : a permutation of the query slots, the order in which workgroups take them (heaviest first);
+ *   idx, cnt [n_queries, k] int32     : for query q up to k rows v != u with c = |X_u & X_v| > 0, best first by `measure`, ties to the smaller
+ *                                       row id; cnt holds c; unused slots are idx = -1, cnt = 0.  Every word is written exactly once, also
+ *                                       for an empty query row or a query id outside [0, n_rows); nothing else is written, no workspace.
+ * The order is decided in 64-bit integers (cosine: c1^2 d2 against c2^2 d1; Jaccard: c1 (du + d2 - c2) against c2 (du + d1 - c1)), so the
+ * result is a function of the input alone.  max_degree is the largest row degree, stated by the caller: past arl_cooccur_max_degree(measure)
+ * (2^20 for cosine, 2^31 - 1 otherwise) the keys could overflow and the entry returns ARL_E_RANGE; the entry trusts the value (it cannot read
+ * device memory without a synchronise), and with a max_degree below the true one the order of the lists is unspecified.  1 <= k <= arl_cooccur_max_k() = 128;
+ * tile_rows = 0 takes arl_cooccur_default_tile_rows() (16 384 candidate rows = 64 KiB of LDS counters, two workgroups per CU), at most
+ * arl_cooccur_max_tile_rows() (36 864).  Negative sizes, k < 1 or an unknown measure: ARL_E_ARG; k, tile_rows, n_rows, n_cols, n_queries,
+ * n_queries * k >= 2^31 or max_degree past their limits: ARL_E_RANGE; a NULL rowptr, colptr, idx or cnt with n_queries > 0: ARL_E_NULL; all
+ * before any launch.  Ids outside [0, n_rows) / [0, n_cols) are skipped. */
+#define ARL_COOCCUR_COUNT 0
+#define ARL_COOCCUR_COSINE 1
+#define ARL_COOCCUR_JACCARD 2
+int64_t arl_cooccur_max_k(void);
+int64_t arl_cooccur_max_tile_rows(void);
+int64_t arl_cooccur_default_tile_rows(void);
+int64_t arl_cooccur_max_degree(int32_t measure);
+int arl_cooccur_topk_i32(const int64_t *rowptr, const int32_t *col, const int64_t *colptr, const int32_t *irow, int64_t n_rows, int64_t n_cols,
+                         const int32_t *rows, int64_t n_queries, int64_t k, int32_t measure, int64_t max_degree, const int32_t *order,
+                         int64_t tile_rows, int32_t *idx, int32_t *cnt, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Item-table exchange of the user-sharded step (no reference counterpart: main.py:19 pins one device).
  * One process per GPU.  arl_comm_unique_id (rank 0) -> the 128 bytes travel to every rank by any side channel (torch.distributed
  * broadcast) -> arl_comm_init on every rank.  arl_allreduce_item_f32 sum-all-reduces buf[0, n_elems) IN PLACE, asynchronously on `stream`,
