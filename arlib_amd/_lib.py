@@ -194,6 +194,12 @@ _SIGS = {
     'arl_cooccur_default_tile_rows': (_i64, []),
     'arl_cooccur_max_degree': (_i64, [_i32]),
     'arl_cooccur_topk_i32': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i64, _vp, _i64, _vp, _vp, _vp]),
+    'arl_itemknn_max_k': (_i64, []),
+    'arl_itemknn_max_n': (_i64, []),
+    'arl_itemknn_max_targets': (_i64, []),
+    'arl_itemknn_max_tile_items': (_i64, []),
+    'arl_itemknn_default_tile_items': (_i64, []),
+    'arl_itemknn_score_topk_i64': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     'arl_comm_load': (C.c_int, [C.c_char_p]),
     'arl_comm_unique_id': (C.c_int, [_vp]),
     'arl_comm_init': (C.c_int, [_vp, _i64, _i64, _i64, C.POINTER(C.c_void_p)]),

@@ -2,5 +2,6 @@ from .DirectAU import DirectAU  # noqa: F401  (a model without a counterpart fil
 from .APR import APR  # noqa: F401  (likewise: the defended victim)
 from .MultVAE import MultVAE  # noqa: F401  (likewise: the inductive victim)
 from .iALS import iALS  # noqa: F401  (likewise: the ALS-trained WRMF victim)
+from .ItemKNN import ItemKNN  # noqa: F401  (likewise: the neighbourhood victim of the shilling attacks)
 
-__all__ = ['DirectAU', 'APR', 'MultVAE', 'iALS']
+__all__ = ['DirectAU', 'APR', 'MultVAE', 'iALS', 'ItemKNN']

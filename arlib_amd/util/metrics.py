@@ -120,6 +120,9 @@ class AttackMetric(object):
             import torch
             from .. import ops
             rm = self.recommendModel
+            if hasattr(rm, 'topk_all_users'):                 # a model without embedding tables ranks for itself (recommender/ItemKNN.py)
+                self._rank = np.asarray(rm.topk_all_users(max(self.top)))
+                return self._rank
             uid = torch.tensor([rm.data.user[u] for u in rm.data.user], dtype=torch.long, device=rm.user_emb.device)
             Pu, Pi = rm.user_emb[uid].contiguous(), rm.item_emb.contiguous()
             k = min(max(self.top), Pi.shape[0])
@@ -178,6 +181,9 @@ class TargetRankMetric(object):
             import torch
             from .. import ops
             rm = self.recommendModel
+            if hasattr(rm, 'target_ranks'):                   # likewise
+                self._rank = np.asarray(rm.target_ranks(self.targetItem, mask_train=self.mask_train))
+                return self._rank
             dev = rm.user_emb.device
             ids = [rm.data.user[u] for u in rm.data.user]
             uid = torch.tensor(ids, dtype=torch.long, device=dev)

@@ -960,6 +960,35 @@ int arl_cooccur_topk_i32(const int64_t *rowptr, const int32_t *col, const int64_
                          int64_t tile_rows, int32_t *idx, int32_t *cnt, arl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact fixed-point item-kNN scores and the full-catalogue top-N (csrc/arl_itemknn.hip; no reference counterpart: the scoring step of
+ * arlib_amd/recommender/ItemKNN.py on the neighbour lists arl_cooccur_topk_i32 writes for the transposed matrix).  X is n_users x n_items:
+ *   rowptr [n_users + 1], col [nnz]   : X as CSR; every row a set, columns ascending and distinct within a row (the entry trusts this);
+ *   nbr_idx, nbr_w [n_items, k] int32 : neighbour r of item j and its non-negative weight; a slot with nbr_idx < 0 is unused, its weight ignored;
+ *   rows [n_queries] (optional)       : the query users, any order, repeats allowed; NULL = query q is user q;
+ *   tgt_id, tgt_col [n_targets]       : the distinct target items in ascending order and the column of `rank` each one is reported in;
+ *   order [n_queries] (optional)      : a permutation of the query slots, the order in which workgroups take them (heaviest first);
+ *   idx int32, score int64 [n_queries, n] : s(u, i) = sum over j in X_u, r < k of [nbr_idx[j, r] == i] nbr_w[j, r], exact in 64 bits; every
+ *                                       item is a candidate (score 0 included; with mask_profile != 0 the items of X_u are not), ordered by
+ *                                       (score descending, id ascending); the n best, best first; unused slots are idx = -1, score = 0;
+ *   rank int32 [n_queries, n_targets] : the number of candidates that beat the target, -1 for a target the mask excludes.
+ * Every output word is written exactly once, also for an empty profile, a profile holding every item or a query id outside [0, n_users);
+ * nothing else is written, no workspace.  The result is a function of the input alone.  1 <= k <= arl_itemknn_max_k() = 128,
+ * 1 <= n <= arl_itemknn_max_n() = 128, n_targets <= arl_itemknn_max_targets() = 64; tile_items = 0 takes arl_itemknn_default_tile_items()
+ * (8 160 items = 64 KiB of 64-bit LDS accumulators, two workgroups per CU), at most arl_itemknn_max_tile_items() (18 400).  Negative sizes,
+ * k < 1 or n < 1: ARL_E_ARG; k, n, n_targets, tile_items, n_users, n_items, n_queries, n_queries * n or n_queries * n_targets >= 2^31 past
+ * their limits: ARL_E_RANGE; a NULL rowptr, idx or score, NULL neighbour lists with n_items > 0 or NULL target arguments with n_targets > 0,
+ * with n_queries > 0: ARL_E_NULL; all before any launch.  Neighbour ids outside [0, n_items) are skipped. */
+int64_t arl_itemknn_max_k(void);
+int64_t arl_itemknn_max_n(void);
+int64_t arl_itemknn_max_targets(void);
+int64_t arl_itemknn_max_tile_items(void);
+int64_t arl_itemknn_default_tile_items(void);
+int arl_itemknn_score_topk_i64(const int64_t *rowptr, const int32_t *col, int64_t n_users, int64_t n_items, const int32_t *nbr_idx,
+                               const int32_t *nbr_w, int64_t k, const int32_t *rows, int64_t n_queries, int64_t n, int32_t mask_profile,
+                               const int32_t *tgt_id, const int32_t *tgt_col, int64_t n_targets, const int32_t *order, int64_t tile_items,
+                               int32_t *idx, int64_t *score, int32_t *rank, arl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Item-table exchange of the user-sharded step (no reference counterpart: main.py:19 pins one device).
  * One process per GPU.  arl_comm_unique_id (rank 0) -> the 128 bytes travel to every rank by any side channel (torch.distributed
  * broadcast) -> arl_comm_init on every rank.  arl_allreduce_item_f32 sum-all-reduces buf[0, n_elems) IN PLACE, asynchronously on `stream`,
