@@ -200,6 +200,9 @@ _SIGS = {
     'arl_itemknn_max_tile_items': (_i64, []),
     'arl_itemknn_default_tile_items': (_i64, []),
     'arl_itemknn_score_topk_i64': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'arl_userknn_max_tile_items': (_i64, []),
+    'arl_userknn_default_tile_items': (_i64, []),
+    'arl_userknn_score_topk_i64': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     'arl_comm_load': (C.c_int, [C.c_char_p]),
     'arl_comm_unique_id': (C.c_int, [_vp]),
     'arl_comm_init': (C.c_int, [_vp, _i64, _i64, _i64, C.POINTER(C.c_void_p)]),

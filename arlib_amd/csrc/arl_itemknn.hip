@@ -22,6 +22,16 @@
 //     query's 2N list words and T rank words, each written exactly once (the padding idx = -1, score = 0 included, also for an empty profile,
 //     a profile holding the whole catalogue or a query id outside [0, n_users));
 //   * neighbour ids outside [0, n_items) never match a tile or a target and so never become an address; rowptr and col are trusted.
+//
+// The user side (arlib_amd/userknn.py, recommender/UserKNN.py) is the same kernel with another filling of the accumulators
+// and the target scores; the side is a template parameter, the selection is shared.  There user u lists k neighbour users nbr_idx[u, r] with
+// weights nbr_w[u, r], and
+//     s(u, i) = sum over r < k with v = nbr_idx[u, r] in [0, n_users) of nbr_w[u, r] [i in P_v].
+// A cursor, an end and the weight per slot live in LDS.  Per tile [t0, t1) waves go over the slots and lanes over the neighbour's row from its
+// cursor: the row is sorted, so its entries below t1 are a prefix, every one gets the slot's weight added to its accumulator, and the cursor
+// moves on by the ballot's count until a chunk reaches t1 or the row's end.  Every entry of a neighbour's row is read once, plus at most one
+// re-read chunk per tile seam.  The targets' scores come from one bisection per (slot, target) pair in the neighbour's row.  A neighbour id
+// outside [0, n_users) leaves its slot empty and never becomes an address.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -47,6 +57,12 @@ constexpr int kDefaultTile = 8160;                              // 16 512 + 8 * 
 enum { LIST_N = 0, PEND_N = 1, CAND = 2, LIVE_T = 3 };
 static_assert(kFixedBytes % 16 == 0 && (int64_t)kFixedBytes + 8ll * kMaxTile <= kLdsBytes, "LDS budget");
 static_assert((int64_t)kFixedBytes + 8ll * kDefaultTile <= kLdsBytes / 2, "two workgroups per CU at the default tile");
+// the user side adds a cursor and an end (64-bit) and a weight per neighbour slot
+constexpr int kUserFixedBytes = kFixedBytes + (8 + 8 + 4) * kMaxK;                                                  // 19 072
+constexpr int kUserMaxTile = 18096;                             // 19 072 + 8 * 18 096 = 163 840
+constexpr int kUserDefaultTile = 7856;                          // 19 072 + 8 * 7 856 = 81 920 = 80 KiB: two workgroups per CU
+static_assert(kUserFixedBytes % 16 == 0 && (int64_t)kUserFixedBytes + 8ll * kUserMaxTile <= kLdsBytes, "LDS budget, user side");
+static_assert((int64_t)kUserFixedBytes + 8ll * kUserDefaultTile <= kLdsBytes / 2, "two workgroups per CU at the default tile, user side");
 
 // a = (sa, ia) comes before b: the larger score, then the smaller id
 __device__ __forceinline__ bool beats(int64_t sa, int ia, int64_t sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
@@ -89,18 +105,23 @@ __device__ __forceinline__ int lower_bound_lds(const int *a, int n, int x) {
     return lo;
 }
 
-__global__ __launch_bounds__(kBlk) void itemknn_score_topk_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                                   const int32_t *__restrict__ nbr_idx, const int32_t *__restrict__ nbr_w,
-                                                                   const int32_t *__restrict__ rows, const int32_t *__restrict__ order,
-                                                                   const int32_t *__restrict__ tgt_id, const int32_t *__restrict__ tgt_col,
-                                                                   int n_users, int n_items, int n_q, int K, int N, int NT, int mask_profile,
-                                                                   int T, int32_t *__restrict__ idx, int64_t *__restrict__ score,
-                                                                   int32_t *__restrict__ rank) {
+// kUser = false: the item side, lists indexed by item.  kUser = true: the user side, lists indexed by user.  The two instances differ in how the
+// accumulators and the target scores are filled and in nothing else.
+template <bool kUser>
+__global__ __launch_bounds__(kBlk) void knn_score_topk_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                               const int32_t *__restrict__ nbr_idx, const int32_t *__restrict__ nbr_w,
+                                                               const int32_t *__restrict__ rows, const int32_t *__restrict__ order,
+                                                               const int32_t *__restrict__ tgt_id, const int32_t *__restrict__ tgt_col,
+                                                               int n_users, int n_items, int n_q, int K, int N, int NT, int mask_profile,
+                                                               int T, int32_t *__restrict__ idx, int64_t *__restrict__ score,
+                                                               int32_t *__restrict__ rank) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     int64_t *es = (int64_t *)lds, *tsc = es + kEnt, *ss = tsc + kMaxT;
     int *ei = (int *)(ss + kMaxT), *tgi = ei + kEnt, *tgc = tgi + kMaxT, *tlive = tgc + kMaxT, *si = tlive + kMaxT, *sc = si + kMaxT;
     int *hist = sc + kMaxT, *hdr = hist + kHist;
-    int64_t *acc = (int64_t *)(lds + kFixedBytes);
+    int64_t *acc = (int64_t *)(lds + (kUser ? kUserFixedBytes : kFixedBytes));
+    int64_t *cur = (int64_t *)(lds + kFixedBytes), *cend = cur + kMaxK;     // user side only: the slots' cursors, ends and weights
+    uint32_t *cw = (uint32_t *)(cend + kMaxK);
     const int slot = order ? order[blockIdx.x] : (int)blockIdx.x;
     if ((unsigned)slot >= (unsigned)n_q) return;                // `order` is a permutation of the slots; anything else is dropped
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -112,20 +133,44 @@ __global__ __launch_bounds__(kBlk) void itemknn_score_topk_kernel(const int64_t 
     if (ue < ub) ue = ub;
     if (tid == 0) hdr[LIST_N] = 0, hdr[PEND_N] = 0, hdr[CAND] = 0, hdr[LIVE_T] = 0;
     for (int j = tid; j < kHist; j += kBlk) hist[j] = 0;
+    if constexpr (kUser) {                                      // a slot without a neighbour in [0, n_users) is an empty row
+        if (tid < K) {
+            const int v = (unsigned)u < (unsigned)n_users ? nbr_idx[(int64_t)u * K + tid] : -1;
+            int64_t b = 0, e = 0;
+            uint32_t w = 0;
+            if ((unsigned)v < (unsigned)n_users) b = rowptr[v], e = rowptr[v + 1], w = (uint32_t)nbr_w[(int64_t)u * K + tid];
+            cur[tid] = b, cend[tid] = e < b ? b : e, cw[tid] = w;
+        }
+    }
 
     // ---- the targets: their scores from a first pass over the profile, then the live ones sorted best first
     int nlive = 0;
     if (NT > 0) {                                               // uniform over the workgroup
         if (tid < NT) tgi[tid] = tgt_id[tid], tgc[tid] = tgt_col[tid], tsc[tid] = 0;
         __syncthreads();
-        for (int64_t p = ub + wv; p < ue; p += kWaves) {
-            const int j = col[p];
-            if ((unsigned)j >= (unsigned)n_items) continue;
-            for (int r = lane; r < K; r += 64) {
-                const int i = nbr_idx[(int64_t)j * K + r];
-                if ((unsigned)i >= (unsigned)n_items) continue;
-                const int t = lower_bound_lds(tgi, NT, i);
-                if (t < NT && tgi[t] == i) atomicAdd((unsigned long long *)&tsc[t], (unsigned long long)(uint32_t)nbr_w[(int64_t)j * K + r]);
+        if constexpr (kUser) {                                  // every (slot, target) pair bisects the target in the neighbour's row
+            for (int pr = tid; pr < K * NT; pr += kBlk) {
+                const int r = pr / NT, t = pr - r * NT;
+                const int x = tgi[t];
+                int64_t lo = cur[r];
+                const int64_t e = cend[r];
+                int64_t hi = e;
+                while (lo < hi) {
+                    const int64_t mid = (lo + hi) >> 1;
+                    if (col[mid] < x) lo = mid + 1; else hi = mid;
+                }
+                if (lo < e && col[lo] == x) atomicAdd((unsigned long long *)&tsc[t], (unsigned long long)cw[r]);
+            }
+        } else {
+            for (int64_t p = ub + wv; p < ue; p += kWaves) {
+                const int j = col[p];
+                if ((unsigned)j >= (unsigned)n_items) continue;
+                for (int r = lane; r < K; r += 64) {
+                    const int i = nbr_idx[(int64_t)j * K + r];
+                    if ((unsigned)i >= (unsigned)n_items) continue;
+                    const int t = lower_bound_lds(tgi, NT, i);
+                    if (t < NT && tgi[t] == i) atomicAdd((unsigned long long *)&tsc[t], (unsigned long long)(uint32_t)nbr_w[(int64_t)j * K + r]);
+                }
             }
         }
         if (tid < NT) {                                         // a target inside the profile is masked
@@ -158,13 +203,31 @@ __global__ __launch_bounds__(kBlk) void itemknn_score_topk_kernel(const int64_t 
         __syncthreads();                                        // the previous tile's scan is over
         for (int i = tid; i < tl; i += kBlk) acc[i] = 0;
         __syncthreads();
-        for (int64_t p = ub + wv; p < ue; p += kWaves) {
-            const int j = col[p];
-            if ((unsigned)j >= (unsigned)n_items) continue;
-            for (int r = lane; r < K; r += 64) {
-                const int i = nbr_idx[(int64_t)j * K + r];
-                if ((unsigned)(i - t0) < (unsigned)tl)
-                    atomicAdd((unsigned long long *)&acc[i - t0], (unsigned long long)(uint32_t)nbr_w[(int64_t)j * K + r]);
+        if constexpr (kUser) {
+            for (int r = wv; r < K; r += kWaves) {              // uniform over the wave: the ballot below sees every lane
+                int64_t c = cur[r];
+                const int64_t e = cend[r];
+                const unsigned long long w = cw[r];
+                while (c < e) {
+                    const int64_t p = c + lane;
+                    const int i = p < e ? col[p] : INT_MAX;
+                    const bool below = p < e && i < t1;         // the row is sorted: these lanes are a prefix of the chunk
+                    if (below && (unsigned)(i - t0) < (unsigned)tl) atomicAdd((unsigned long long *)&acc[i - t0], w);
+                    const int n = __popcll(__ballot(below));
+                    c += n;
+                    if (n < 64) break;                          // the chunk reached t1 or the row's end
+                }
+                if (lane == 0) cur[r] = c;                      // this wave alone reads and writes slot r
+            }
+        } else {
+            for (int64_t p = ub + wv; p < ue; p += kWaves) {
+                const int j = col[p];
+                if ((unsigned)j >= (unsigned)n_items) continue;
+                for (int r = lane; r < K; r += 64) {
+                    const int i = nbr_idx[(int64_t)j * K + r];
+                    if ((unsigned)(i - t0) < (unsigned)tl)
+                        atomicAdd((unsigned long long *)&acc[i - t0], (unsigned long long)(uint32_t)nbr_w[(int64_t)j * K + r]);
+                }
             }
         }
         __syncthreads();
@@ -260,6 +323,36 @@ __global__ __launch_bounds__(kBlk) void itemknn_score_topk_kernel(const int64_t 
     }
 }
 
+// the checks and the launch of both C entries; the lists have one row per item (item side) or per user (user side)
+template <bool kUser>
+int score_topk(const int64_t *rowptr, const int32_t *col, int64_t n_users, int64_t n_items, const int32_t *nbr_idx, const int32_t *nbr_w, int64_t k,
+               const int32_t *rows, int64_t n_queries, int64_t n, int32_t mask_profile, const int32_t *tgt_id, const int32_t *tgt_col,
+               int64_t n_targets, const int32_t *order, int64_t tile_items, int32_t *idx, int64_t *score, int32_t *rank, arl_stream_t stream) {
+    constexpr int kFixed = kUser ? kUserFixedBytes : kFixedBytes, kTileMax = kUser ? kUserMaxTile : kMaxTile;
+    constexpr int kTileDefault = kUser ? kUserDefaultTile : kDefaultTile;
+    if (n_users < 0 || n_items < 0 || n_queries < 0 || k < 1 || n < 1 || n_targets < 0 || tile_items < 0) return ARL_E_ARG;
+    if (k > kMaxK || n > kMaxN || n_targets > kMaxT || tile_items > kTileMax) return ARL_E_RANGE;
+    if (n_users > 0x7fffffffll || n_items > 0x7fffffffll || n_queries > 0x7fffffffll) return ARL_E_RANGE;
+    if (n_queries * n > 0x7fffffffll || n_queries * n_targets > 0x7fffffffll) return ARL_E_RANGE;
+    if (n_queries == 0) return ARL_OK;
+    if (!rowptr || !idx || !score) return ARL_E_NULL;           // col may be NULL for a matrix without entries
+    if ((kUser ? n_users : n_items) > 0 && (!nbr_idx || !nbr_w)) return ARL_E_NULL;
+    if (n_targets > 0 && (!tgt_id || !tgt_col || !rank)) return ARL_E_NULL;
+    int64_t T = tile_items ? tile_items : kTileDefault;
+    if (T > n_items) T = n_items > 0 ? n_items : 1;
+    const size_t shm = (size_t)kFixed + 8 * (size_t)((T + 1) & ~1ll);
+    const void *fn = (const void *)knn_score_topk_kernel<kUser>;
+    if (shm > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        if (e != hipSuccess) return (int)e;
+    }
+    const dim3 grid((unsigned)n_queries), block(kBlk);
+    hipLaunchKernelGGL(knn_score_topk_kernel<kUser>, grid, block, shm, (hipStream_t)stream, rowptr, col, nbr_idx, nbr_w, rows, order, tgt_id, tgt_col,
+                       (int)n_users, (int)n_items, (int)n_queries, (int)k, (int)n, (int)n_targets, mask_profile ? 1 : 0, (int)T, idx, score, rank);
+    hipError_t e = hipGetLastError();
+    return e != hipSuccess ? (int)e : ARL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -274,27 +367,19 @@ int arl_itemknn_score_topk_i64(const int64_t *rowptr, const int32_t *col, int64_
                                const int32_t *nbr_w, int64_t k, const int32_t *rows, int64_t n_queries, int64_t n, int32_t mask_profile,
                                const int32_t *tgt_id, const int32_t *tgt_col, int64_t n_targets, const int32_t *order, int64_t tile_items,
                                int32_t *idx, int64_t *score, int32_t *rank, arl_stream_t stream) {
-    if (n_users < 0 || n_items < 0 || n_queries < 0 || k < 1 || n < 1 || n_targets < 0 || tile_items < 0) return ARL_E_ARG;
-    if (k > kMaxK || n > kMaxN || n_targets > kMaxT || tile_items > kMaxTile) return ARL_E_RANGE;
-    if (n_users > 0x7fffffffll || n_items > 0x7fffffffll || n_queries > 0x7fffffffll) return ARL_E_RANGE;
-    if (n_queries * n > 0x7fffffffll || n_queries * n_targets > 0x7fffffffll) return ARL_E_RANGE;
-    if (n_queries == 0) return ARL_OK;
-    if (!rowptr || !idx || !score) return ARL_E_NULL;           // col may be NULL for a matrix without entries
-    if (n_items > 0 && (!nbr_idx || !nbr_w)) return ARL_E_NULL;
-    if (n_targets > 0 && (!tgt_id || !tgt_col || !rank)) return ARL_E_NULL;
-    int64_t T = tile_items ? tile_items : kDefaultTile;
-    if (T > n_items) T = n_items > 0 ? n_items : 1;
-    const size_t shm = (size_t)kFixedBytes + 8 * (size_t)((T + 1) & ~1ll);
-    const void *fn = (const void *)itemknn_score_topk_kernel;
-    if (shm > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-    }
-    const dim3 grid((unsigned)n_queries), block(kBlk);
-    hipLaunchKernelGGL(itemknn_score_topk_kernel, grid, block, shm, (hipStream_t)stream, rowptr, col, nbr_idx, nbr_w, rows, order, tgt_id, tgt_col,
-                       (int)n_users, (int)n_items, (int)n_queries, (int)k, (int)n, (int)n_targets, mask_profile ? 1 : 0, (int)T, idx, score, rank);
-    hipError_t e = hipGetLastError();
-    return e != hipSuccess ? (int)e : ARL_OK;
+    return score_topk<false>(rowptr, col, n_users, n_items, nbr_idx, nbr_w, k, rows, n_queries, n, mask_profile, tgt_id, tgt_col, n_targets, order,
+                             tile_items, idx, score, rank, stream);
+}
+
+int64_t arl_userknn_max_tile_items(void) { return kUserMaxTile; }
+int64_t arl_userknn_default_tile_items(void) { return kUserDefaultTile; }
+
+int arl_userknn_score_topk_i64(const int64_t *rowptr, const int32_t *col, int64_t n_users, int64_t n_items, const int32_t *nbr_idx,
+                               const int32_t *nbr_w, int64_t k, const int32_t *rows, int64_t n_queries, int64_t n, int32_t mask_profile,
+                               const int32_t *tgt_id, const int32_t *tgt_col, int64_t n_targets, const int32_t *order, int64_t tile_items,
+                               int32_t *idx, int64_t *score, int32_t *rank, arl_stream_t stream) {
+    return score_topk<true>(rowptr, col, n_users, n_items, nbr_idx, nbr_w, k, rows, n_queries, n, mask_profile, tgt_id, tgt_col, n_targets, order,
+                            tile_items, idx, score, rank, stream);
 }
 
 }  // extern "C"

@@ -81,11 +81,12 @@ def float_score(score, measure):
     return s.astype(np.float64) if measure == 'count' else s.astype(np.float64) / SCALE
 
 
-def _lists(nbr_idx, nbr_w, n_items, dev, who):
-    """The neighbour lists as int32 [n_items, k] tensors on dev, checked: ids below n_items, weights of the used slots non-negative."""
+def _lists(nbr_idx, nbr_w, n_items, dev, who, side='n_items'):
+    """The neighbour lists as int32 [n_items, k] tensors on dev, checked: ids below n_items, weights of the used slots non-negative.  (The user
+    side, arlib_amd/userknn.py, passes n_users and side='n_users'.)"""
     ni, nw = torch.as_tensor(nbr_idx).to(dev), torch.as_tensor(nbr_w).to(dev)
     if ni.dim() != 2 or nw.shape != ni.shape or ni.shape[0] != n_items or any(t.dtype.is_floating_point or t.dtype == torch.bool for t in (ni, nw)):
-        raise ValueError('%s: integer nbr_idx and nbr_w of shape [n_items = %d, k] needed' % (who, n_items))
+        raise ValueError('%s: integer nbr_idx and nbr_w of shape [%s = %d, k] needed' % (who, side, n_items))
     k = int(ni.shape[1])
     if k < 1:
         raise ValueError('%s: k = %d, k >= 1 needed' % (who, k))
@@ -98,15 +99,15 @@ def _lists(nbr_idx, nbr_w, n_items, dev, who):
     return ni.to(torch.int32).contiguous(), nw.to(torch.int32).contiguous(), k   # after the range checks: a 64-bit value must not wrap into the range
 
 
-def _validated(rowptr, col, n_users, n_items, nbr_idx, nbr_w, N, rows, targets, tile_items, dev):
+def _validated(rowptr, col, n_users, n_items, nbr_idx, nbr_w, N, rows, targets, tile_items, dev, who='knn_score_topk', max_tile=KNN_MAX_TILE_ITEMS,
+               user_side=False):
     n_users, n_items, N = int(n_users), int(n_items), int(N)
-    who = 'knn_score_topk'
     if n_users < 0 or n_items < 0 or n_users >= 2 ** 31 or n_items >= 2 ** 31:
         raise ValueError('%s: n_users = %d, n_items = %d' % (who, n_users, n_items))
     if N < 1:
         raise ValueError('%s: N = %d, N >= 1 needed' % (who, N))
-    if tile_items is not None and not 1 <= int(tile_items) <= KNN_MAX_TILE_ITEMS:
-        raise ValueError('%s: tile_items = %d outside [1, %d]' % (who, int(tile_items), KNN_MAX_TILE_ITEMS))
+    if tile_items is not None and not 1 <= int(tile_items) <= max_tile:
+        raise ValueError('%s: tile_items = %d outside [1, %d]' % (who, int(tile_items), max_tile))
     rp = torch.as_tensor(rowptr).to(dev, torch.int64).contiguous()
     ci = torch.as_tensor(col).to(dev)
     nnz = ci.numel()
@@ -117,7 +118,7 @@ def _validated(rowptr, col, n_users, n_items, nbr_idx, nbr_w, N, rows, targets, 
     if nnz and (int(ci.min()) < 0 or int(ci.max()) >= n_items):
         raise ValueError('%s: item id outside [0, %d)' % (who, n_items))
     ci = ci.to(torch.int32).contiguous()
-    ni, nw, k = _lists(nbr_idx, nbr_w, n_items, dev, who)
+    ni, nw, k = _lists(nbr_idx, nbr_w, n_users, dev, who, 'n_users') if user_side else _lists(nbr_idx, nbr_w, n_items, dev, who)
     rw = None
     if rows is not None:
         rw = torch.as_tensor(rows).to(dev).contiguous()
@@ -205,6 +206,46 @@ def weight_matrix(nbr_idx, nbr_w, n_items):
     return sp.csr_matrix((nw[used], (j, ni[used])), shape=(n_items, n_items), dtype=np.int64)
 
 
+def _host_queries(rows, targets, n_users, n_items, who):
+    """(query users int64 [Q], targets int64 [T] or None) of a host route, checked."""
+    if rows is None:
+        q_rows = np.arange(n_users, dtype=np.int64)
+    else:
+        q_rows = np.asarray(rows)
+        if q_rows.ndim != 1 or q_rows.dtype.kind not in 'iu' or (q_rows.size and (q_rows.min() < 0 or q_rows.max() >= n_users)):
+            raise ValueError('%s: rows must be a 1-d list of ids in [0, %d)' % (who, n_users))
+        q_rows = q_rows.astype(np.int64)
+    tg = None
+    if targets is not None:
+        tg = np.asarray(targets)
+        if tg.ndim != 1 or (tg.size and tg.dtype.kind not in 'iu') or (tg.size and (tg.min() < 0 or tg.max() >= n_items)) or len(np.unique(tg)) != len(tg):
+            raise ValueError('%s: targets must be distinct ids in [0, %d)' % (who, n_items))
+        tg = tg.astype(np.int64)
+    return q_rows, tg
+
+
+def _select(S, tg, idx, score, rank):
+    """The selection of both host routes (this module's and arlib_amd/userknn.py's) on a dense chunk S int64 [q, n_items] of scores with the
+    excluded items set to -1: one lexsort on (id, -score) fills idx, score [q, N] (preset to -1, 0), and the candidates that beat each target
+    are counted into rank [q, T] (preset to -1)."""
+    q, n_items = S.shape
+    m = min(idx.shape[1], n_items)
+    n_cand = (S >= 0).sum(1)
+    if m:
+        ids = np.arange(n_items, dtype=np.int64)
+        p = np.lexsort((np.broadcast_to(ids, S.shape).ravel(), -S.ravel(), np.repeat(np.arange(q), n_items)))
+        top = (p.reshape(q, n_items)[:, :m] % n_items).astype(np.int64)
+        ts = np.take_along_axis(S, top, 1)
+        ok = np.arange(m)[None, :] < n_cand[:, None]
+        idx[:, :m] = np.where(ok, top, -1)
+        score[:, :m] = np.where(ok, ts, 0)
+    if tg is not None:
+        for t, item in enumerate(tg.tolist()):
+            st = S[:, item]
+            beat = ((S > st[:, None]) & (S >= 0)).sum(1) + (S[:, :item] == st[:, None]).sum(1)
+            rank[:, t] = np.where(st >= 0, beat, -1)
+
+
 def knn_score_topk_host(interact, nbr_idx, nbr_w, N, rows=None, mask_profile=False, targets=None, chunk_rows=2048):
     """The contract of knn_score_topk on the host, as numpy arrays (idx int32 [Q, N], score int64 [Q, N], rank int32 [Q, T] or None): scipy's
     product X[rows] @ W of the binarised matrix with W = weight_matrix (int64, exact), made dense chunk_rows query rows at a time, excluded
@@ -217,41 +258,15 @@ def knn_score_topk_host(interact, nbr_idx, nbr_w, N, rows=None, mask_profile=Fal
     n_users, n_items = X.shape
     ni, nw, _ = _lists(nbr_idx, nbr_w, n_items, torch.device('cpu'), 'knn_score_topk_host')
     W = weight_matrix(ni.numpy(), nw.numpy(), n_items)
-    if rows is None:
-        q_rows = np.arange(n_users, dtype=np.int64)
-    else:
-        q_rows = np.asarray(rows)
-        if q_rows.ndim != 1 or q_rows.dtype.kind not in 'iu' or (q_rows.size and (q_rows.min() < 0 or q_rows.max() >= n_users)):
-            raise ValueError('knn_score_topk_host: rows must be a 1-d list of ids in [0, %d)' % n_users)
-        q_rows = q_rows.astype(np.int64)
-    tg = None
-    if targets is not None:
-        tg = np.asarray(targets)
-        if tg.ndim != 1 or (tg.size and tg.dtype.kind not in 'iu') or (tg.size and (tg.min() < 0 or tg.max() >= n_items)) or len(np.unique(tg)) != len(tg):
-            raise ValueError('knn_score_topk_host: targets must be distinct ids in [0, %d)' % n_items)
-        tg = tg.astype(np.int64)
+    q_rows, tg = _host_queries(rows, targets, n_users, n_items, 'knn_score_topk_host')
     Q = len(q_rows)
     idx, score = np.full((Q, N), -1, np.int32), np.zeros((Q, N), np.int64)
     rank = None if tg is None else np.full((Q, len(tg)), -1, np.int32)
-    ids = np.arange(n_items, dtype=np.int64)
-    m = min(N, n_items)
     for b in range(0, Q, max(int(chunk_rows), 1)):
         qr = q_rows[b:b + max(int(chunk_rows), 1)]
         Xq = X[qr]
         S = np.asarray((Xq @ W).todense(), dtype=np.int64)
         if mask_profile:
             S[np.repeat(np.arange(len(qr)), np.diff(Xq.indptr)), Xq.indices] = -1
-        n_cand = (S >= 0).sum(1)
-        if m:
-            p = np.lexsort((np.broadcast_to(ids, S.shape).ravel(), -S.ravel(), np.repeat(np.arange(len(qr)), n_items)))
-            top = (p.reshape(len(qr), n_items)[:, :m] % n_items).astype(np.int64)
-            ts = np.take_along_axis(S, top, 1)
-            ok = np.arange(m)[None, :] < n_cand[:, None]
-            idx[b:b + len(qr), :m] = np.where(ok, top, -1)
-            score[b:b + len(qr), :m] = np.where(ok, ts, 0)
-        if tg is not None:
-            for t, item in enumerate(tg.tolist()):
-                st = S[:, item]
-                beat = ((S > st[:, None]) & (S >= 0)).sum(1) + (S[:, :item] == st[:, None]).sum(1)
-                rank[b:b + len(qr), t] = np.where(st >= 0, beat, -1)
+        _select(S, tg, idx[b:b + len(qr)], score[b:b + len(qr)], None if rank is None else rank[b:b + len(qr)])
     return idx, score, rank

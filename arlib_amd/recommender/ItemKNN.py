@@ -9,18 +9,15 @@ floor(sim 2^30); 'count': the co-occurrence count), the scores and lists itemknn
 id ascending)); floats are formed from those integers in one place (itemknn.float_score), so a GPU run and a host run agree bit for bit
 (DESIGN.md section 3t).  There are no embedding tables, no epochs, no sampler and no optimizer: train() builds the lists once, and nothing is
 drawn from `random` or torch's generator."""
-import sys
-
 import numpy as np
 import scipy.sparse as sp
 import torch
 
 from .. import itemknn, neighbours
-from ..util.metrics import ranking_evaluation, ranking_evaluation_topk
-from ._base import Recommender
+from ._knn import KNNRecommender
 
 
-class ItemKNN(Recommender):
+class ItemKNN(KNNRecommender):
     knn_k = 50                        # neighbours kept per item; args.knn_k overrides
     knn_measure = 'cosine'            # 'count', 'cosine' or 'jaccard'; args.knn_measure overrides
     knn_shrink = 0.0                  # added to the similarity's denominator; args.knn_shrink overrides
@@ -36,10 +33,7 @@ class ItemKNN(Recommender):
         self.nbr_idx = self.nbr_cnt = self.nbr_w = self.item_deg = None
         self._X = self._W = self._dev_lists = None
 
-    # ---- the model: the training matrix and the item-side lists
-    def _matrix(self):
-        return neighbours.binary_csr(self.data.interaction_mat)
-
+    # ---- the model: the item-side lists of the training matrix
     def fit(self):
         """The item-side neighbour lists of the current training matrix: (nbr_idx, nbr_cnt int32 [I, knn_k], item_deg int64 [I]) and nbr_w."""
         X = self._matrix()
@@ -52,10 +46,6 @@ class ItemKNN(Recommender):
         self.nbr_w = itemknn.knn_weights(self.nbr_idx, self.nbr_cnt, self.item_deg, self.knn_measure, self.knn_shrink)
         self._X, self._W = X, None
         self._dev_lists = None
-
-    def _fitted(self):
-        if self.nbr_idx is None:
-            raise RuntimeError('ItemKNN: train() first')
 
     def _score_topk(self, rows, N, mask, targets=None):
         """knn_score_topk on the fitted lists, as numpy arrays."""
@@ -81,50 +71,7 @@ class ItemKNN(Recommender):
         print('training: neighbour lists of', self.nbr_idx.shape[0], 'items, k =', self.knn_k, 'measure:', self.knn_measure)
         self.evaluate(0)
 
-    def save(self):
-        pass                                                      # one fit, nothing to keep beside it
-
-    # ---- evaluation
-    def _test_topk(self):
-        """(test users in test_set order, top-max_N item ids [n, k] with -1 past the candidates, float scores) with the training items masked."""
-        users = list(self.data.test_set)
-        if not users:
-            return users, np.zeros((0, 0), np.int64), np.zeros((0, 0), np.float64)
-        idx, score, _ = self._score_topk([self.data.user[u] for u in users], min(self.max_N, len(self.data.item)), True)
-        return users, idx.astype(np.int64), itemknn.float_score(score, self.knn_measure)
-
-    def _rec_list(self, users, idx, val):
-        return {user: [(self.data.id2item[int(i)], float(s)) for i, s in zip(idx[r], val[r]) if i >= 0] for r, user in enumerate(users)}
-
-    def _measures(self, users, idx, val, Ns):
-        if users and bool((idx >= 0).all()):
-            return ranking_evaluation_topk(self.data, idx, Ns)
-        return ranking_evaluation(self.data.test_set, self._rec_list(users, idx, val), Ns)     # a user with fewer candidates than N: the plain form
-
-    def evaluate(self, epoch):
-        print('Evaluating the model...')
-        users, idx, val = self._test_topk()
-        sys.stdout.write('\rProgress: [' + '+' * 50 + ']100%\n')
-        measure = self._measures(users, idx, val, [self.max_N])
-        performance = {}
-        for m in measure[1:]:
-            k, v = m.strip().split(':')
-            performance[k] = float(v)
-        self.bestPerformance = [epoch + 1, performance]
-        print('-' * 120)
-        print('Real-Time Ranking Performance ' + ' (Top-' + str(self.max_N) + ' Item Recommendation)')
-        measure = [m.strip() for m in measure[1:]]
-        print('*Current Performance*')
-        print('Epoch:', str(epoch + 1) + ',', '  |  '.join(measure))
-        print('-' * 120)
-        return measure
-
-    def test(self):
-        users, idx, val = self._test_topk()
-        rec_list = self._rec_list(users, idx, val)
-        sys.stdout.write('\rProgress: [' + '+' * 50 + ']100%\n')
-        return rec_list, self._measures(users, idx, val, self.topN)
-
+    # ---- evaluation: KNNRecommender's, on _score_topk above
     def predict(self, u):
         """The dense float score row of user u (a raw id) over the whole catalogue."""
         self._fitted()
@@ -132,19 +79,6 @@ class ItemKNN(Recommender):
             self._W = itemknn.weight_matrix(self.nbr_idx, self.nbr_w, self._X.shape[1])
         row = np.asarray((self._X[self.data.get_user_id(u)] @ self._W).todense(), dtype=np.int64).ravel()
         return itemknn.float_score(row, self.knn_measure)
-
-    # ---- the hooks util.metrics.AttackMetric / TargetRankMetric look for
-    def _all_users(self):
-        return [self.data.user[u] for u in self.data.user]
-
-    def topk_all_users(self, k, mask_train=False):
-        """int64 [U, min(k, I)]: the k best items of every user of data.user, in that order; -1 past the candidates."""
-        return self._score_topk(self._all_users(), min(int(k), len(self.data.item)), bool(mask_train))[0].astype(np.int64)
-
-    def target_ranks(self, targets, mask_train=False):
-        """int32 [U, T]: the 0-based rank of every target (internal item ids, distinct) for every user of data.user, -1 where masked."""
-        tg = np.asarray([int(t) for t in targets], np.int64)
-        return self._score_topk(self._all_users(), 1, bool(mask_train), tg)[2]
 
     def neighbours_of(self, item):
         """[(raw item id, float similarity)] of the fitted list of `item` (a raw id), best first."""

@@ -3,5 +3,6 @@ from .APR import APR  # noqa: F401  (likewise: the defended victim, DESIGN.md se
 from .MultVAE import MultVAE  # noqa: F401  (likewise: the inductive victim)
 from .iALS import iALS  # noqa: F401  (likewise: the ALS-trained WRMF victim)
 from .ItemKNN import ItemKNN  # noqa: F401  (likewise: the neighbourhood victim of the shilling attacks)
+from .UserKNN import UserKNN  # noqa: F401  (likewise: the user-based neighbourhood victim)
 
-__all__ = ['DirectAU', 'APR', 'MultVAE', 'iALS', 'ItemKNN']
+__all__ = ['DirectAU', 'APR', 'MultVAE', 'iALS', 'ItemKNN', 'UserKNN']

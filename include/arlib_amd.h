@@ -988,6 +988,21 @@ int arl_itemknn_score_topk_i64(const int64_t *rowptr, const int32_t *col, int64_
                                const int32_t *tgt_id, const int32_t *tgt_col, int64_t n_targets, const int32_t *order, int64_t tile_items,
                                int32_t *idx, int64_t *score, int32_t *rank, arl_stream_t stream);
 
+/* The user side of the same kernel (the scoring step of arlib_amd/recommender/UserKNN.py on the lists arl_cooccur_topk_i32 writes for the matrix
+ * itself).  The argument list is arl_itemknn_score_topk_i64's with the lists indexed by user: nbr_idx, nbr_w [n_users, k] int32, neighbour
+ * user r of user u and its non-negative weight, and
+ *   s(u, i) = sum over r < k with v = nbr_idx[u, r] in [0, n_users) of nbr_w[u, r] [i in P_v],
+ * taken as written: a neighbour named in two slots counts twice, a slot naming u itself counts.  Candidates, order, outputs, limits on k, n and
+ * n_targets and the error codes are those above (NULL neighbour lists with n_users > 0: ARL_E_NULL); neighbour ids outside [0, n_users) are
+ * skipped.  The fixed LDS grows by a cursor, an end and a weight per slot: tile_items = 0 takes arl_userknn_default_tile_items() (7 856 items,
+ * 80 KiB in all, two workgroups per CU), at most arl_userknn_max_tile_items() (18 096). */
+int64_t arl_userknn_max_tile_items(void);
+int64_t arl_userknn_default_tile_items(void);
+int arl_userknn_score_topk_i64(const int64_t *rowptr, const int32_t *col, int64_t n_users, int64_t n_items, const int32_t *nbr_idx,
+                               const int32_t *nbr_w, int64_t k, const int32_t *rows, int64_t n_queries, int64_t n, int32_t mask_profile,
+                               const int32_t *tgt_id, const int32_t *tgt_col, int64_t n_targets, const int32_t *order, int64_t tile_items,
+                               int32_t *idx, int64_t *score, int32_t *rank, arl_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Item-table exchange of the user-sharded step (no reference counterpart: main.py:19 pins one device).
  * One process per GPU.  arl_comm_unique_id (rank 0) -> the 128 bytes travel to every rank by any side channel (torch.distributed
